@@ -7,9 +7,11 @@ One step = forward + backward of loss = mse(x_hat, x) + vq_loss, global-norm cli
 in HBM before the timed region.  Multi-GPU: one process per GPU (torch.distributed.run), RCCL all-reduce of the
 flat gradient buffer every step, per-rank batch fixed (weak scaling).
 
-Prints ONE JSON line (rank 0) with the roofline of the dominant kernel (the MFMA GEMM family, timed live with
-HIP events on its launch stream over the timed region) and a CPU baseline (the oracle port on the host cores,
-bounded sample, rank 0 at N=1 only).
+A plain run sets up, warms up, times `--steps` steps and prints ONE JSON line (rank 0) with the headline figure;
+`--dump-outputs DIR` also writes what the last timed step computed.  `--full` adds everything else to the line: the
+roofline of the dominant kernel (the MFMA GEMM family, timed live with HIP events on its launch stream in eager
+steps after the timed region), the VQ kernel alone, the fp32 / stress / Transformer sub-lines, a CPU baseline (the
+oracle port on the host cores, bounded sample, rank 0 at N=1 only) and the detail file.
 """
 from __future__ import annotations
 
@@ -38,6 +40,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=1024, help="windows per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the per-GEMM roofline pass, the VQ kernel "
+                         "alone, the fp32, stress and Transformer sub-lines and the CPU baseline, and write --detail "
+                         "(the --no-* switches below trim this set; without --full none of it runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (the loss it returned, the updated "
+                         "parameters) as DIR/<name>.npy in float32; that step starts from the seeded initial state, "
+                         "reset with the clock stopped")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-profile", action="store_true", help="skip the live per-GEMM event timing")
@@ -67,22 +77,31 @@ def build_model(dev, K=512, D=64):
     return m.to(dev).train()
 
 
-def _timed_steps(step, warmup, steps, world):
-    """warmup untimed steps, then `steps` timed ones between barrier + synchronize; max over ranks (seconds)."""
+def _timed_steps(step, warmup, steps, world, before_last=None):
+    """warmup untimed steps, then `steps` timed ones between barrier + synchronize; max over ranks (seconds).
+    `before_last` (--dump-outputs: the reset of the training state) runs before the last timed step with the clock
+    stopped: the steps before it and the last one are timed as two stretches, each between synchronizes."""
     for i in range(warmup):
         step(i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
+    el = 0.0
     t0 = time.perf_counter()
     for i in range(steps):
+        if before_last is not None and i == steps - 1:
+            torch.cuda.synchronize()
+            el += time.perf_counter() - t0
+            before_last()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
         step(i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    t = torch.tensor([time.perf_counter() - t0], device="cuda", dtype=torch.float64)
+    t = torch.tensor([el + time.perf_counter() - t0], device="cuda", dtype=torch.float64)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(t.item())
@@ -307,35 +326,84 @@ def cpu_baseline(seconds):
             "reference": REFERENCE_CPU}
 
 
-def vqvae_workload(dev, rank, world, args, dtype, steps, warmup, profile=True, K=512, D=64):
+DUMP_MAX_BYTES = 32 << 20     # all of --dump-outputs (the float32 payload) stays under this
+
+
+def dump_outputs(out_dir, model, loss):
+    """What a caller of the timed step holds after its last call, as out_dir/<name>.npy (float32): `loss`, the
+    tensor the step returned, and `params`, every parameter as the update left it, flattened and joined in
+    named_parameters() order.  An array over its share
+    of DUMP_MAX_BYTES is written as a fixed sample of its elements (flat indices drawn once from a seeded generator,
+    sorted: the same ones in every run and every build)."""
+    import numpy as np
+    arrays = {"loss": loss.detach().reshape(1),
+              "params": torch.cat([p.detach().to(torch.float32).reshape(-1) for p in model.parameters()])}
+    cap = DUMP_MAX_BYTES // 4 // len(arrays)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        if t.numel() > cap:
+            keep = np.sort(np.random.default_rng(0).choice(t.numel(), cap, replace=False))
+            t = t[torch.from_numpy(keep).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(torch.float32).cpu().numpy())
+
+
+def reset_training_state(model, opt, params0):
+    """Put the model and its optimizer back where setup left them: the initial parameters (`params0`, a copy of the
+    optimizer's flat buffer), zero RAdam moments and step count, the dropout counter at zero, and the GEMM operand
+    copies relaid from those parameters into their own buffers (a captured step graph keeps reading them).  The
+    gradients are zero already (the update zeroes them)."""
+    F = opt._flat
+    F["p"].copy_(params0)
+    F["m"].zero_()
+    F["v"].zero_()
+    F["step"].zero_()
+    opt._step_count = 0
+    if getattr(model, "_rng_counter", None) is not None:
+        model._rng_counter.zero_()
+    for st in model.__dict__.get("_operand_sets", {}).values():
+        st.refresh(force=True)
+
+
+def vqvae_workload(dev, rank, world, args, dtype, steps, warmup, profile=True, K=512, D=64, dump=None):
     """configs[1]: one step = fwd + bwd (mse + VQ loss) + clip 0.7 + RAdam over B windows per GPU, inputs resident
-    in HBM, captured as HIP graphs; operands `dtype` (bf16 opt-in or exact fp32).  Returns (elapsed seconds,
-    per-GEMM profile list or None, eager seconds/step of the profiled pass)."""
+    in HBM, captured as HIP graphs; operands `dtype` (bf16 opt-in or exact fp32).  `dump`: the directory
+    dump_outputs writes to right after the timed steps (None: no dump, False: a rank that only takes part).  The last
+    timed step then starts from the state setup left (reset_training_state), not from where the steps before it got
+    to: the f32 atomic adds of the backward land in another order every run, with bf16 operands such a last-bit
+    difference flips bf16 roundings, and after a few steps two runs of one build are 1e-4 apart; one step from the
+    seeded state is the same in every run down to those last bits.  Returns (elapsed seconds, per-GEMM profile list
+    or None, eager seconds/step of the profiled pass)."""
     from arcweld import kernels
     from arcweld.precision import operands
     from arcweld.trainer import Trainer
     with operands(dtype):
         model = build_model(dev, K, D)
         trainer = Trainer(gradient_clip_val=0.7)
-        trainer.setup_optimizer(model)
+        opt = trainer.setup_optimizer(model)
+        params0 = opt.flatten()[0].clone() if dump is not None else None
         scale = 1.0 / world
         gen_ = torch.Generator(device=dev)
         gen_.manual_seed(1000 + rank)
         batches = [torch.randn(args.batch, 200, 2, device=dev, generator=gen_) for _ in range(4)]
         use_graph = not args.no_graph
 
+        last = {}
+
         def eager_step(i):
-            trainer.micro_step(model, batches[i % len(batches)], i, scale)
+            last["loss"] = trainer.micro_step(model, batches[i % len(batches)], i, scale)
             trainer.optimizer_step(model)
 
         def step(i):
             if use_graph:
-                trainer.graphed_step(model, batches[i % len(batches)], scale)
+                last["loss"] = trainer.graphed_step(model, batches[i % len(batches)], scale)
             else:
                 eager_step(i)
 
         # graphed_step runs 2 eager warm-up calls and captures on the 3rd: >= 3 untimed calls keep the capture out
-        elapsed = _timed_steps(step, max(warmup, 3 if use_graph else 0), steps, world)
+        elapsed = _timed_steps(step, max(warmup, 3 if use_graph else 0), steps, world,
+                               (lambda: reset_training_state(model, opt, params0)) if dump is not None else None)
+        if dump:
+            dump_outputs(dump, model, last["loss"])
         # per-GEMM HIP events cannot sit inside a captured graph: the kernel durations for the roofline come from a
         # profiled eager pass over the same workload right after the timed region (GPU-side durations are the
         # same; rocprofv3 in profiles/ cross-checks them against the graph replays)
@@ -640,17 +708,22 @@ def main():
         return
 
     # headline: configs[1] in bf16 (BASELINE.json names bf16 for it; an explicit opt-in, arcweld.precision)
+    full = args.full
     elapsed, prof, prof_el = vqvae_workload(dev, rank, world, args, torch.bfloat16, args.steps, args.warmup,
-                                            profile=not args.no_profile)
+                                            profile=full and not args.no_profile,
+                                            dump=args.dump_outputs and (args.dump_outputs if rank == 0 else False))
     value = world * args.batch * args.steps / elapsed
-    pmc, traffic_src = pmc_traffic("pmc_traffic_vqvae.json")
-    roofline = gemm_roofline(prof, prof_el, elapsed, args.steps, BF16_PEAK_TFLOPS, "bf16", pmc,
-                             traffic_src) if prof else None
+    roofline = None
+    if prof:
+        pmc, traffic_src = pmc_traffic("pmc_traffic_vqvae.json")
+        roofline = gemm_roofline(prof, prof_el, elapsed, args.steps, BF16_PEAK_TFLOPS, "bf16", pmc, traffic_src)
 
-    extra = {"vq_kernel": vq_kernel_roofline(dev, args.batch * 16, 512, 64)}
+    extra = {}
+    if full:
+        extra["vq_kernel"] = vq_kernel_roofline(dev, args.batch * 16, 512, 64)
     if prof:
         extra["vq_kernel"]["in_step"] = vq_in_step(prof)
-    if not args.no_fp32:
+    if full and not args.no_fp32:
         # the same step with exact-fp32 operands (the default numerics, the reference's): priced against the
         # 157.3 TF fp32 MFMA roof
         n32 = max(20, args.steps)           # steady state: >= 20 timed replays after the capture (warm-up >= 3)
@@ -659,16 +732,16 @@ def main():
         extra["fp32"] = {"value": round(world * args.batch * n32 / el32, 2), "unit": "windows/s",
                          "ms_per_step": round(el32 * 1e3 / n32, 3), "steps": n32, "dtype": "f32",
                          "roofline": gemm_roofline(prof32, pel32, el32, n32, FP32_PEAK_TFLOPS, "f32") if prof32 else None}
-    if not args.no_stress:
+    if full and not args.no_stress:
         extra["stress"] = stress_workload(dev, rank, world, args)
-    if not args.no_transformer:
+    if full and not args.no_transformer:
         from arcweld.precision import operands
         with operands(torch.bfloat16):
             _transformer_lines(extra, dev, rank, world, args)
 
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.cpu_seconds)
         line = {"metric": METRIC, "value": round(value, 2), "unit": "windows/s", "n_gpus": world,
                 "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed * 1e3 / args.steps, 3),
@@ -686,12 +759,13 @@ def main():
                            "operands": "bf16 (opt-in), fp32 accumulation and master weights"},
                 "roofline": roofline, "cpu_baseline": cpu, **extra,
                 "launch": "eager" if args.no_graph else "hip-graph"}
-        detail = os.path.join(REPO, args.detail) if args.detail else None
+        detail = args.detail if full else None
         if detail:
-            os.makedirs(os.path.dirname(detail), exist_ok=True)
-            with open(detail, "w") as f:
+            path = os.path.join(REPO, detail)
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            with open(path, "w") as f:
                 json.dump(line, f, indent=1)
-        print(json.dumps(compact_line(line, args.detail)), flush=True)
+        print(json.dumps(compact_line(line, detail)), flush=True)
     if distributed:
         dist.destroy_process_group()
 
