@@ -106,6 +106,16 @@ int aw_gemm_grouped(const aw_gemm_args* args, int n, void* stream);
 /* Tile policy knob: 0 = automatic (256x128 tiles for bf16 launches that fill the chip, else 128x128), 128 or 256 =
  * force that tile for every eligible launch (bf16, non-ragged) -- used by the tests to cover both pipelines. */
 int aw_gemm_set_tile(int bm);
+/* Which instantiation aw_gemm would launch for these args: no launch, no device call (the operand pointers are only
+ * tested for NULL and alignment).  layout: 0 NN, 1 NN + implicit conv, 2 NT, 3 NT + implicit conv, 4 TN, 5 TT,
+ * 6 TT + implicit conv on B (N = a_trans b_trans); epi: the epilogue code of the launch (the EpiBits of
+ * csrc/gemm_core.h; 1 << 31 = the generic body that reads every field at run time, 1 << 14 = accumulate / split-K);
+ * tile_rows: 128 or 256 (aw_gemm_set_tile applies); specialised: 1 when a compiled specialisation exists for
+ * (dtype, layout, tile, epi), 0 when the launch takes the generic body; ragged: an operand extent that is not whole
+ * 16-B chunks (register staging); splits: split-K slices.  Any output pointer may be NULL.  M == 0 or N == 0 (no
+ * launch) reports tile_rows = 0, splits = 0, the generic code.  Returns AW_OK or the status aw_gemm would return. */
+int aw_gemm_describe(const aw_gemm_args* args, int* layout, uint32_t* epi, int* tile_rows, int* specialised,
+                     int* ragged, int* splits);
 /* Weight-gradient kernel policy for the grouped decoder k = 3 launches (model/vq_vae_patch_embedd.py:60-74 grads):
  * 0 = automatic (the 8-wave ping-pong kernel when the shape qualifies and fills the chip), 1 = force it whenever the
  * shape qualifies, -1 = always the generic grouped GEMM (tests, A/B). */

@@ -96,6 +96,8 @@ SIGNATURES = {
     "aw_gemm_workspace": [ctypes.POINTER(GemmArgs)],
     "aw_gemm_grouped": [ctypes.POINTER(GemmArgs), c_int, c_p],
     "aw_gemm_set_tile": [c_int],
+    "aw_gemm_describe": [ctypes.POINTER(GemmArgs), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_uint32),
+                         ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)],
     "aw_gemm_set_wgrad_policy": [c_int],
     "aw_wgrad_batch_workspace": [ctypes.POINTER(GemmArgs), c_int],
     "aw_wgrad_batch": [ctypes.POINTER(GemmArgs), c_int, c_p, c_i64, c_p],

@@ -26,7 +26,8 @@ Layout layout_of(const aw_gemm_args& a) {
 // compile-time epilogue code of a launch (EP_GENERIC when no specialisation can apply)
 uint32_t epi_code(const aw_gemm_args& a, const GemmP& P, bool ragged) {
   if (P.splits > 1 || a.accumulate) return ragged ? EP_GENERIC : EP_ACCUM;
-  if (ragged || !P.vec || a.N % 4 != 0 || a.alpha != 1.f) return EP_GENERIC;
+  // (the fused A-row sums are compiled into the generic and accumulate bodies only: gemm_core.h ROWSUM_OK)
+  if (ragged || !P.vec || a.N % 4 != 0 || a.alpha != 1.f || a.a_rowsum) return EP_GENERIC;
   uint32_t c = 0;
   if (a.bias) c |= EP_BIAS;
   if (a.bias && a.bias_mod > 0) c |= EP_BIASMOD;
@@ -46,11 +47,21 @@ uint32_t epi_code(const aw_gemm_args& a, const GemmP& P, bool ragged) {
   return c;
 }
 
+// the gemm_fast_* instantiation of (dtype, layout, P.bm, code), if one exists: launched when `launch`, only looked
+// up otherwise (dispatch and aw_gemm_describe share this, so the query cannot drift from the launch)
+bool fast_kernel(const GemmP& P, hipStream_t s, bool is_bf16, Layout ly, uint32_t code, bool launch) {
+  if (code == EP_ACCUM || code == EP_GENERIC) return false;
+  if (ly == L_NN || ly == L_NN_CONV) return launch_fast_fwd(P, s, is_bf16, ly, code, launch);
+  if (ly == L_NT || ly == L_NT_CONV) return launch_fast_bwd(P, s, is_bf16, ly, code, launch);
+  return false;
+}
+
 template <typename T>
 void dispatch(const GemmP& P, hipStream_t s, bool ragged) {
   const Layout ly = layout_of(P.a);
   uint32_t code = epi_code(P.a, P, ragged);
   constexpr bool BF = sizeof(T) == 2;
+  if (fast_kernel(P, s, BF, ly, code, true)) return;
   if (code == EP_ACCUM) {
     switch (ly) {
       case L_TN: launch_tiled<T, L_TN, EP_ACCUM>(P, s); return;
@@ -58,9 +69,6 @@ void dispatch(const GemmP& P, hipStream_t s, bool ragged) {
       case L_TT_KCONV: launch_tiled<T, L_TT_KCONV, EP_ACCUM>(P, s); return;
       default: break;
     }
-  } else if (code != EP_GENERIC) {
-    if ((ly == L_NN || ly == L_NN_CONV) && launch_fast_fwd(P, s, BF, ly, code)) return;
-    if ((ly == L_NT || ly == L_NT_CONV) && launch_fast_bwd(P, s, BF, ly, code)) return;
   }
   switch (ly) {
     case L_NN: launch_generic<T, L_NN>(P, s, ragged); break;
@@ -353,6 +361,37 @@ extern "C" int aw_gemm_ws(const aw_gemm_args* args, float* ws, int64_t ws_elems,
     hipLaunchKernelGGL(gemm_reduce_kernel, dim3((int)g), dim3(256), 0, s, P.ws, P.splits, a.M, a.N, a);
   }
   return aw::check_launch("aw_gemm");
+}
+
+// Host-only: the checks, the plan and the code of aw_gemm_ws, and the lookup dispatch() makes, without a launch.
+extern "C" int aw_gemm_describe(const aw_gemm_args* args, int* layout, uint32_t* epi, int* tile_rows,
+                                int* specialised, int* ragged, int* splits) {
+  if (!args) {
+    aw::set_error("aw_gemm_describe: null args");
+    return AW_ERR_ARG;
+  }
+  const aw_gemm_args& a = *args;
+  if (int st = validate(a)) return st;
+  const bool rg = is_ragged(a);
+  const Layout ly = layout_of(a);
+  uint32_t code = EP_GENERIC;
+  int bm = 0, nsplit = 0;
+  bool fast = false;
+  if (a.M > 0 && a.N > 0) {   // an empty product launches nothing (aw_gemm_ws returns before its plan)
+    GemmP P;
+    plan(a, 1, false, P);
+    code = epi_code(a, P, rg);
+    fast = fast_kernel(P, nullptr, a.a_dtype == AW_BF16, ly, code, false);
+    bm = P.bm;
+    nsplit = P.splits;
+  }
+  if (layout) *layout = (int)ly;
+  if (epi) *epi = code;
+  if (tile_rows) *tile_rows = bm;
+  if (specialised) *specialised = fast ? 1 : 0;
+  if (ragged) *ragged = rg ? 1 : 0;
+  if (splits) *splits = nsplit;
+  return AW_OK;
 }
 
 extern "C" int aw_gemm_grouped(const aw_gemm_args* args, int n, void* stream) {

@@ -917,10 +917,11 @@ inline void launch_tiled(const GemmP& P, hipStream_t s) {
 }
 
 // Specialised-epilogue launchers (gemm_fast_fwd.hip, gemm_fast_bwd.hip): return false when (dtype, layout,
-// code) has no compiled specialisation, so the caller falls back to the EP_GENERIC kernel.
-bool launch_fast_fwd(const GemmP& P, hipStream_t s, bool is_bf16, Layout ly, uint32_t code);
-bool launch_fast_bwd(const GemmP& P, hipStream_t s, bool is_bf16, Layout ly, uint32_t code);
-bool launch_fast_256(const GemmP& P, hipStream_t s, Layout ly, uint32_t code);   // bf16, P.bm == 256
+// code) has no compiled specialisation, so the caller falls back to the EP_GENERIC kernel.  launch = false answers
+// the same question without launching anything (aw_gemm_describe).
+bool launch_fast_fwd(const GemmP& P, hipStream_t s, bool is_bf16, Layout ly, uint32_t code, bool launch);
+bool launch_fast_bwd(const GemmP& P, hipStream_t s, bool is_bf16, Layout ly, uint32_t code, bool launch);
+bool launch_fast_256(const GemmP& P, hipStream_t s, Layout ly, uint32_t code, bool launch);   // bf16, P.bm == 256
 // The grouped decoder k = 3 weight gradient on the 8-wave ping-pong kernel (wgrad.hip); false when the shape or
 // the policy (aw_gemm_set_wgrad_policy) rules it out (the caller then runs the generic grouped GEMM).
 bool wgrad_conv3_try(const aw_gemm_args* args, int n, hipStream_t s);

@@ -5,10 +5,11 @@
 
 namespace awg {
 
+// launch = false only looks the instantiation up (aw_gemm_describe): one case list serves both
 #define AW_FAST_CASE256(T, LY, CODE) \
-  case (CODE): launch_kernel<T, LY, false, (CODE), 256>(P, s); return true;
+  case (CODE): if (launch) launch_kernel<T, LY, false, (CODE), 256>(P, s); return true;
 
-bool launch_fast_256(const GemmP& P, hipStream_t s, Layout ly, uint32_t code) {
+bool launch_fast_256(const GemmP& P, hipStream_t s, Layout ly, uint32_t code, bool launch) {
   switch (ly) {
     case L_NN:
       switch (code) {

@@ -4,11 +4,12 @@
 
 namespace awg {
 
+// launch = false only looks the instantiation up (aw_gemm_describe): one case list serves both
 #define AW_FAST_CASE128(T, LY, CODE) \
-  case (CODE): launch_kernel<T, LY, false, (CODE), 128>(P, s); return true;
+  case (CODE): if (launch) launch_kernel<T, LY, false, (CODE), 128>(P, s); return true;
 
-bool launch_fast_bwd(const GemmP& P, hipStream_t s, bool is_bf16, Layout ly, uint32_t code) {
-  if (P.bm == 256) return is_bf16 && launch_fast_256(P, s, ly, code);
+bool launch_fast_bwd(const GemmP& P, hipStream_t s, bool is_bf16, Layout ly, uint32_t code, bool launch) {
+  if (P.bm == 256) return is_bf16 && launch_fast_256(P, s, ly, code, launch);
   if (is_bf16 && ly == L_NT) {
     switch (code) {
       AW_BWD_CONV_CODES(AW_FAST_CASE128, bf16, L_NT)
