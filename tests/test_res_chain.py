@@ -48,34 +48,13 @@ def _weights(R, seed, taps):
     return w1, w2, b1, b2
 
 
-def _gemm_conv(taps, d):
-    """aw_gemm's implicit conv form of a decoder conv (forward d = 1, input gradient d = -1); {} for the encoder."""
-    return dict(conv=(H, SEG, d, 0)) if taps == 3 else {}
-
-
 def _unfused_fwd(a0, x0, w1, w2, b1, b2, p, seeds, ctr, taps):
-    """arcweld/vqvae.py's per-conv launches (the ARCWELD_ENC_CHAIN=0 / ARCWELD_DEC_CHAIN=0 path)."""
-    K = _k()
-    N = a0.shape[0]
-    R = len(w1)
-    e = lambda: torch.empty(N, H, device="cuda", dtype=BF)  # noqa: E731
-    cv = _gemm_conv(taps, 1)
-    xs, a0s, hs, a1s = [x0], [a0], [], []
-    for r in range(R):
-        h, a1 = e(), e()
-        K.gemm(a0s[r], w1[r], N, H, taps * H, bias=b1[r], C=h, C2=a1, c2_mode=1, **cv)
-        if r < R - 1:
-            xn, an = e(), e()
-            K.gemm(a1, w2[r], N, H, taps * H, bias=b2[r], drop=(p, seeds[r]), seed_ptr=ctr, resid=xs[r], C=xn, C2=an,
-                   c2_mode=1, **cv)
-        else:
-            xn, an = None, e()
-            K.gemm(a1, w2[r], N, H, taps * H, bias=b2[r], drop=(p, seeds[r]), seed_ptr=ctr, resid=xs[r], C=an, **cv)
-        xs.append(xn)
-        a0s.append(an)
-        hs.append(h)
-        a1s.append(a1)
-    return hs, a1s, xs[1:], a0s[1:]
+    """The shipped per-conv route (arcweld/resstack.py; the ARCWELD_ENC_CHAIN=0 / ARCWELD_DEC_CHAIN=0 path of the
+    training step): (h, a1, x, a) per block."""
+    from arcweld import resstack
+    _, _, sv = resstack.forward(resstack.Geometry(taps, H, SEG), x0, a0, list(zip(w1, w2)), list(zip(b1, b2)),
+                                T=BF, RT=BF, p_drop=p, seeds=seeds, ctr=ctr)
+    return sv.hs, sv.a1s, sv.xs[1:], sv.a0s[1:]
 
 
 def _same(got, want, what):

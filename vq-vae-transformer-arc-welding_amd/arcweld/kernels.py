@@ -326,9 +326,10 @@ def res_chain_fwd(a0, x0, w1, w2, b1, b2, dh, a1, dx, a, drop=(0.0, None), seed_
     g.store_policy = _chain_store_policy()
     g.drop_masks = ptr(masks)
     _maybe_timed(stream, "gemm_bf16", _chain_flops(R, N, H, taps, seg),
-                 lambda sp: call("aw_res_chain_fwd", ctypes.byref(g), sp), f"res_chain_fwd_kernel<{int(taps)}>",
-                 _nbytes([a0, x0, masks] + list(w1) + list(w2) + list(b1) + list(b2) + list(dh) + list(a1) +
-                         list(dx)[:-1] + list(a)))
+                 lambda sp: call("aw_res_chain_fwd", ctypes.byref(g), sp),
+                 lambda: (f"res_chain_fwd_kernel<{int(taps)}>",
+                          _nbytes([a0, x0, masks] + list(w1) + list(w2) + list(b1) + list(b2) + list(dh) + list(a1) +
+                                  list(dx)[:-1] + list(a))))
 
 
 def res_chain_bwd(gx, gxo, w1t, w2t, dh, x0, dx, gh, gxo_out, drop_p=0.0, masks=None, taps=1, seg=16, stream=None):
@@ -352,9 +353,10 @@ def res_chain_bwd(gx, gxo, w1t, w2t, dh, x0, dx, gh, gxo_out, drop_p=0.0, masks=
     g.store_policy = _chain_store_policy()
     g.drop_masks = ptr(masks)
     _maybe_timed(stream, "gemm_bf16", _chain_flops(R, N, H, taps, seg),
-                 lambda sp: call("aw_res_chain_bwd", ctypes.byref(g), sp), f"res_chain_bwd_kernel<{int(taps)}>",
-                 _nbytes([gx, gxo, x0, masks] + list(w1t) + list(w2t) + list(dh) + list(dx[1:]) + list(gh) +
-                         list(gxo_out)))
+                 lambda sp: call("aw_res_chain_bwd", ctypes.byref(g), sp),
+                 lambda: (f"res_chain_bwd_kernel<{int(taps)}>",
+                          _nbytes([gx, gxo, x0, masks] + list(w1t) + list(w2t) + list(dh) + list(dx[1:]) + list(gh) +
+                                  list(gxo_out))))
 
 
 def res_pack_weights(src, fwd=None, bwd=None, taps=1, stream=None):
@@ -383,12 +385,12 @@ def vq_forward(z2d, E, zq, idx, counts, sqerr, stream=None, zq_copy=None, count_
     N, D = z2d.shape
     Kc = E.shape[0]
     assert counts.numel() >= count_groups * Kc, "counts: count_groups x K floats"
-    # the pinned kernel (codebook in LDS, f32-input MFMA) serves K <= 512, D in {16, 32, 64} (csrc/vq.hip)
-    name = "vq_fwd_pinned_kernel" if Kc <= 512 and D in (16, 32, 64) else "vq_fwd_kernel"
     _maybe_timed(stream, "vq_fwd", 2.0 * N * Kc * D, lambda sp: call(
         "aw_vq_forward_ex2", ptr(z2d), ptr(E), N, Kc, D, ptr(zq), ptr(idx), ptr(counts), int(count_groups),
-        ptr(sqerr), ptr(zq_copy), dtype_code(zq_copy.dtype) if zq_copy is not None else 0, sp), name,
-        _nbytes([z2d, E, zq, idx, zq_copy]) + 4 * Kc * count_groups)
+        ptr(sqerr), ptr(zq_copy), dtype_code(zq_copy.dtype) if zq_copy is not None else 0, sp),
+        # the pinned kernel (codebook in LDS, f32-input MFMA) serves K <= 512, D in {16, 32, 64} (csrc/vq.hip)
+        lambda: ("vq_fwd_pinned_kernel" if Kc <= 512 and D in (16, 32, 64) else "vq_fwd_kernel",
+                 _nbytes([z2d, E, zq, idx, zq_copy]) + 4 * Kc * count_groups))
 
 
 def vq_finalize(counts, sqerr, N, K, D, beta, loss, perplexity, stream=None, count_groups=1):
@@ -670,12 +672,14 @@ def attn_flops(B, T, n_head, d):
     return 4.0 * B * n_head * (T * (T + 1) / 2) * (d // n_head)
 
 
-def _maybe_timed(stream, tag, flops, fn, name=None, nbytes=None):
+def _maybe_timed(stream, tag, flops, fn, info=None):
+    """Launch fn(stream pointer); when profiling, under _timed with info() = (kernel name, algorithmic HBM bytes),
+    evaluated only then (the byte count walks every tensor of the launch)."""
     if PROFILE is None:
         fn(stream_ptr(stream))
         return
     s = stream if stream is not None else torch.cuda.current_stream()
-    _timed(s, fn, flops, tag, name, nbytes)
+    _timed(s, fn, flops, tag, *(info() if info is not None else ()))
 
 
 def attn_fwd(qkv, B, T, n_head, d, y, lse, drop=(0.0, 0), seed_ptr=None, stream=None):

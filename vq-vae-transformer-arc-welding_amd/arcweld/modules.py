@@ -16,8 +16,8 @@ from __future__ import annotations
 import torch
 
 from . import kernels as K
-from . import vqvae as engine
-from .vqvae import _mix, operand_dtype
+from . import resstack
+from .vqvae import _biases, _grads, _mix, operand_dtype
 
 F32 = torch.float32
 
@@ -49,6 +49,15 @@ def _masked_copy(g, T, p, seed):
     out = torch.empty(N, H, device=g.device, dtype=T)
     dummy = torch.zeros(8, 8, device=g.device, dtype=T)
     K.gemm(dummy, dummy, N, H, 0, resid=g, C2=out, c2_mode=3, drop2=(p, seed))
+    return out
+
+
+def _gelu_operand(x, T):
+    """Operand copy of GELU(x) (dtype T), by the same empty-contraction epilogue (C2 = gelu(v))."""
+    N, H = x.shape
+    out = torch.empty(N, H, device=x.device, dtype=T)
+    dummy = torch.zeros(8, 8, device=x.device, dtype=T)
+    K.gemm(dummy, dummy, N, H, 0, resid=x, C2=out, c2_mode=1)
     return out
 
 
@@ -163,107 +172,50 @@ def resblock(mod, x):
 def _resblock_stack(mod, blocks, sep, batch_norm, dropout_p, x):
     """A stack of ResBlocks (the module `mod` owns their parameters) as one autograd node."""
     T = operand_dtype()
+    convs = [(blk.block[1], blk.block[4]) for blk in blocks]
+    bns = [(blk.block[2], blk.block[5]) for blk in blocks] if batch_norm else None
 
     def fwd(x, save):
         B, H, S = x.shape
-        N = B * S
-        e = _empty(x.device)
-        training = mod.training
-        p = dropout_p if training else 0.0
+        geo = resstack.Geometry(1 if sep else 3, H, S)
+        p = dropout_p if mod.training else 0.0
         seed = _seed(p)
         cur = _tokens(x, F32)
         a0 = _gelu_operand(cur, T)
-        conv = None if sep else (H, S, 1, 0)
-        kd = H if sep else 3 * H
-        sv = _Saved()
-        sv.shape, sv.p, sv.training, sv.blocks = (B, H, S), p, training, []
-        for r, blk in enumerate(blocks):
-            c1, c2 = blk.block[1], blk.block[4]
-            if sep:
-                w1, w2 = e(H, H, dt=T), e(H, H, dt=T)
-                K.weight_relayout_batch([engine._centre_job(c1.weight, w1), engine._centre_job(c2.weight, w2)])
-            else:
-                w1, w2 = e(H, 3 * H, dt=T), e(H, 3 * H, dt=T)
-                K.weight_relayout_batch([engine._conv3_job(c1.weight, 1, w1), engine._conv3_job(c2.weight, 1, w2)])
-            sr = _mix(seed, r)
-            if batch_norm:   # per-token statistics when the tokens run separately, over all positions otherwise
-                gk = {} if conv is None else dict(conv=conv)
-                y, an, bs = engine._bn_block_fwd(a0, cur, w1, w2, kd, gk, c1, c2, (blk.block[2], blk.block[5]),
-                                                 S if sep else 1, training, p, sr, None, T)
-            else:
-                h, a1 = e(N, H, dt=T), e(N, H, dt=T)
-                K.gemm(a0, w1, N, H, kd, conv=conv, bias=c1.bias, C=h, C2=a1, c2_mode=1)
-                y, an = e(N, H), e(N, H, dt=T)
-                K.gemm(a1, w2, N, H, kd, conv=conv, bias=c2.bias, drop=(p, sr), resid=cur, C=y, C2=an, c2_mode=1)
-                bs = (h, a1)
-            if save:
-                sv.blocks.append((cur, a0, bs, w1, w2, sr))
-            cur, a0 = y, an
-        return _channel_major(cur, B, S), sv
+        weights = _BlockOperands(convs, geo.fwd_job, (H, geo.Kd), T)
+        y, _, rec = resstack.forward(geo, cur, a0, weights, _biases(convs), bns, T=T, RT=F32, p_drop=p,
+                                     seeds=[_mix(seed, r) for r in range(len(blocks))], training=mod.training,
+                                     last_operand_only=False, save=save)
+        return _channel_major(y, B, S), ((B, H, S), rec)
 
     def bwd(sv, g, slot, need_x):
-        B, H, S = sv.shape
-        N = B * S
-        p = sv.p
-        e = _empty(g.device)
-        kd = H if sep else 3 * H
-        dconv = None if sep else (H, S, -1, 0)
-        wconv = (H, S, 1, 1)
-
-        def wg(c, A, Bm):
-            if sep:
-                Cw, cm = engine._centre_grad(slot(c.weight))
-                return (A, Bm, H, H, N, dict(a_trans=True, b_trans=True, C=Cw, accumulate=True, col_map=cm,
-                                             a_rowsum=slot(c.bias)))
-            Cw, cm = engine._conv3_grad(slot(c.weight))
-            return (A, Bm, H, 3 * H, N, dict(a_trans=True, b_trans=True, conv=wconv, C=Cw, accumulate=True,
-                                             col_map=cm, a_rowsum=slot(c.bias)))
-
+        (B, H, S), rec = sv
         gy = _tokens(g, F32)
-        nb = len(blocks)
-        go = _masked_copy(gy, T, p, sv.blocks[-1][5]) if (nb and not batch_norm) else None
-        wgrads = []
-        for r in reversed(range(nb)):
-            blk = blocks[r]
-            c1, c2 = blk.block[1], blk.block[4]
-            xr, a0, bs, w1, w2, sr = sv.blocks[r]
-            if sep:
-                W1d, W2d = w1, w2
-            else:   # dgrad operands [3O][I]
-                W1d, W2d = e(3 * H, H, dt=T), e(3 * H, H, dt=T)
-                K.weight_relayout_batch([engine._conv3_job(c1.weight, 2, W1d), engine._conv3_job(c2.weight, 2, W2d)])
-            if batch_norm:
-                gk = {} if dconv is None else dict(conv=dconv)
-                gy, _ = engine._bn_block_bwd(gy, xr, a0, bs, W1d, W2d, kd, gk, wg, c1, c2, (blk.block[2], blk.block[5]),
-                                             S if sep else 1, sv.training, p, sr, None, T, slot, wgrads,
-                                             need_copy=False)
-                continue
-            h, a1 = bs
-            gh = e(N, H, dt=T)
-            K.gemm(go, W2d, N, H, kd, b_trans=True, conv=dconv, pre=h, C=gh)
-            wgrads.append(wg(c2, go, a1))
-            gyn = e(N, H)
-            gon = e(N, H, dt=T) if r > 0 else None
-            K.gemm(gh, W1d, N, H, kd, b_trans=True, conv=dconv, pre=xr, resid=gy, C=gyn, C2=gon,
-                   c2_mode=3 if r > 0 else 0, drop2=(p, sv.blocks[r - 1][5] if r > 0 else 0))
-            wgrads.append(wg(c1, gh, a0))
-            gy, go = gyn, gon
+        go = _masked_copy(gy, T, rec.p_drop, rec.seeds[-1]) if (blocks and not batch_norm) else None
+        # per-token convs: the forward's operands serve; k = 3: the dgrad operands [3O][I]
+        dweights = rec.ws if sep else _BlockOperands(convs, rec.geo.dgrad_job, (3 * H, H), T)
+        gy, _, wgrads = resstack.backward(rec, gy, go, dweights, _grads(convs, slot), bns, slot, r0_copy=False)
         K.gemm_grouped(wgrads)
         if not need_x:
             return None
-        if nb == 0:
+        if not blocks:
             return g
         return _channel_major(gy, B, S).contiguous()
 
     return run(mod, fwd, bwd, x)
 
 
-def _gelu_operand(x, T):
-    N, H = x.shape
-    out = torch.empty(N, H, device=x.device, dtype=T)
-    dummy = torch.zeros(8, 8, device=x.device, dtype=T)
-    K.gemm(dummy, dummy, N, H, 0, resid=x, C2=out, c2_mode=1)
-    return out
+class _BlockOperands:
+    """weights[r] of a stack whose operands are built per call: block r's two conv weights through `job` into fresh
+    `shape` tensors, one relayout launch at the lookup (right before the block's own launches)."""
+
+    def __init__(self, convs, job, shape, T):
+        self.convs, self.job, self.shape, self.T = convs, job, shape, T
+
+    def __getitem__(self, r):
+        ws = [torch.empty(self.shape, device=c.weight.device, dtype=self.T) for c in self.convs[r]]
+        K.weight_relayout_batch([self.job(c.weight, w) for c, w in zip(self.convs[r], ws)])
+        return ws
 
 
 # ------------------------------------------------------------------------------------------- SepCNNBlock
