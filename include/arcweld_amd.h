@@ -524,6 +524,47 @@ int aw_ce_bwd(const float* logits, int64_t R, int V, int64_t ldl, const int64_t*
               void* stream);
 int aw_ce_finalize(const double* loss_sum, const double* count, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ GRU recurrence
+ * One nn.GRU layer (model/gru.py:25,47; torch gate order r, z, n; W_hh (3H, H), b_hh (3H)):
+ *   r = s(gi_r + W_hr h + b_hr)   z = s(gi_z + W_hz h + b_hz)   hn = W_hn h + b_hn
+ *   n = tanh(gi_n + r hn)         h' = (1 - z) n + z h                    (gi = W_ih x + b_ih, from aw_gemm)
+ * Everything that is not recurrent runs through aw_gemm over all B*T rows (input projection, input gradient, weight
+ * gradients).  These entry points are the recurrence: ONE launch per time step, an MFMA GEMM against W_hh
+ * whose epilogue finishes the cell.  No workgroup waits on another and nothing is atomic: same inputs, same bits.
+ * op_dtype selects the GEMM operands: AW_F32 (exact-f32 MFMA; the f32 buffers themselves are the operands) or
+ * AW_BF16 (v_mfma_f32_16x16x32_bf16, f32 accumulation; the kernels write a bf16 copy of what the next GEMM reads).
+ * State, saved gates and gradients are f32 in both modes.
+ * Padded layout (the kernels' own): Hp = H rounded up to a multiple of 32.  Every row below is Hp wide, or 3*Hp /
+ * 4*Hp with gate g at columns [g*Hp, g*Hp + H); rows are contiguous (leading dimension = the row width); columns
+ * >= H of every output are written as exact zeros, and inputs must hold zeros there (they do when they come from
+ * these kernels, or from an aw_gemm against zero-padded weights and bias).  Every buffer is 16-B aligned.  B is
+ * arbitrary (tail rows are guarded).
+ * aw_gru_pack_weights: the operand images of W_hh (f32 (3H, H)) as op_dtype, zero-padded:
+ *   w_fwd [3][Hp][Hp]: w_fwd[g][j][k] = W_hh[g*H + j][k]        (read by aw_gru_step_fwd)
+ *   w_bwd [Hp][3*Hp]:  w_bwd[k][g*Hp + j] = W_hh[g*H + j][k]    (read by aw_gru_step_bwd); either may be NULL. */
+int aw_gru_pack_weights(const float* w_hh, int H, int op_dtype, void* w_fwd, void* w_bwd, void* stream);
+/* One forward step.  h_prev_op (B, Hp, op_dtype) / h_prev (B, Hp, f32): the previous state as GEMM operand and in
+ * f32 (the same buffer in f32 mode); both NULL = zero initial state (GRU.init_hidden, model/gru.py:29-32): no K loop.
+ * gi (B, 3*Hp) f32; b_hh (3H, unpadded).  Writes h (B, Hp) f32, h_op (B, Hp) bf16 = h rounded to nearest even (bf16
+ * mode; NULL in f32 mode), and saved (B, 4*Hp) f32 = [r | z | n | hn] for the backward. */
+int aw_gru_step_fwd(int B, int H, int op_dtype, const void* h_prev_op, const float* h_prev, const void* w_fwd,
+                    const float* gi, const float* b_hh, float* h, void* h_op, float* saved, void* stream);
+/* One backward step, for time step t:
+ *   dh = dgh_next . W_hh + dh_next * z_next + dy        (dgh_next_op (B, 3*Hp, op_dtype), dh_next (B, Hp) and
+ *        saved_next (B, 4*Hp) belong to step t+1: all three NULL at the last step, where the GEMM is skipped;
+ *        dy (B, Hp) f32 is the gradient from the layer above or the head, NULL = none)
+ *   dn = dh (1 - z)(1 - n^2)    dz = dh (h_prev - n) z (1 - z)    dr = dn hn r (1 - r)       (saved = step t's,
+ *        h_prev (B, Hp) f32 = h_{t-1}, NULL = zero state)
+ * Writes dh (B, Hp), dgi = [dr | dz | dn] and dgh = [dr | dz | dn r] (B, 3*Hp) f32, and their bf16 copies dgi_op /
+ * dgh_op (bf16 mode; NULL in f32 mode).  dh may alias dh_next. */
+int aw_gru_step_bwd(int B, int H, int op_dtype, const void* dgh_next_op, const float* dh_next,
+                    const float* saved_next, const void* w_bwd, const float* dy, const float* saved,
+                    const float* h_prev, float* dh, float* dgi, float* dgh, void* dgi_op, void* dgh_op, void* stream);
+/* Bias gradients: db[g*H + j] += sum over the rows of dg (rows, 3*Hp) f32 of column g*Hp + j (db_ih from all steps'
+ * dgi, db_hh from dgh).  From the f32 gate gradients in both operand modes (aw_gemm's fused a_rowsum would sum the
+ * bf16-rounded operand copy); one owner per column and a fixed summation order, so it is deterministic. */
+int aw_gru_bias_grad(const float* dg, int64_t rows, int H, float* db, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

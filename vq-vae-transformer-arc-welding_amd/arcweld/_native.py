@@ -176,6 +176,10 @@ SIGNATURES = {
                           c_p],
     "aw_rvq_residual": [c_p, c_p, c_i64, c_p, c_int, c_p, c_p],
     "aw_rvq_backward": [c_p, c_p, c_p, c_p, c_int, c_i64, c_int, c_f, c_p, c_p],
+    "aw_gru_pack_weights": [c_p, c_int, c_int, c_p, c_p, c_p],
+    "aw_gru_step_fwd": [c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    "aw_gru_bias_grad": [c_p, c_i64, c_int, c_p, c_p],
+    "aw_gru_step_bwd": [c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
 }
 
 RET_I64 = {"aw_gemm_workspace", "aw_wgrad_batch_workspace", "aw_res_dropout_masks_bytes"}

@@ -9,7 +9,10 @@ DistributedSampler per rank.  Here a whole split is resident in HBM (1024 window
   permutation seeded by (seed + epoch), padded to a multiple of world, rank r takes positions r, r+world, ...
 * synthetic_windows -- N(0, 1) 200x2 windows (the StandardScaler'd ASIMoW distribution); the real
   dataset is not available offline.
-* ReconstructionDataModule / LatentPredDataModule -- the datamodule surface the entry scripts use.
+* ReconstructionDataModule / LatentPredDataModule / ClassificationDataModule -- the datamodule surface the entry
+  scripts use.
+* WeightedBatches -- DataLoader(sampler=WeightedRandomSampler(weights, n)) semantics for the classifier's training
+  split: n draws with replacement per epoch.
 """
 from __future__ import annotations
 
@@ -150,3 +153,100 @@ class LatentPredDataModule:
 
     def test_dataloader(self):
         return self._batches(self.test_ds, False, rank=0, world=1)
+
+
+class WeightedBatches:
+    """DataLoader(batch_size, sampler=WeightedRandomSampler(weights, len(weights))) over device tensors: every epoch
+    draws n indices with replacement, probability proportional to ``weights`` (asimow_dataloader.py:123-131)."""
+
+    def __init__(self, tensors, weights, batch_size, seed=0):
+        self.tensors = tuple(tensors)
+        self.weights = torch.as_tensor(weights, dtype=torch.float64).cpu()
+        self.n = len(self.tensors[0])
+        if len(self.weights) != self.n:
+            raise ValueError(f"{len(self.weights)} sampling weights for {self.n} samples")
+        self.batch_size, self.seed, self.epoch = int(batch_size), seed, 0
+
+    def set_epoch(self, epoch):
+        self.epoch = epoch
+
+    def indices(self):
+        g = torch.Generator()
+        g.manual_seed(self.seed + self.epoch)
+        return torch.multinomial(self.weights, self.n, replacement=True, generator=g)
+
+    def __len__(self):
+        return math.ceil(self.n / self.batch_size)
+
+    def __iter__(self):
+        idx = self.indices().to(self.tensors[0].device)
+        for b in range(len(self)):
+            sel = idx[b * self.batch_size:(b + 1) * self.batch_size]
+            yield tuple(t.index_select(0, sel) for t in self.tensors)
+
+
+def class_sampling_weights(labels):
+    """1 - ratio for label 0 and ratio for label 1, ratio = mean(labels == 0) (get_sampling_weights,
+    asimow_dataloader.py:107-121; arcweld.asimow.sampling_weights on host arrays)."""
+    from .asimow import sampling_weights
+    return torch.as_tensor(sampling_weights(labels.detach().cpu().numpy()))
+
+
+@torch.no_grad()
+def latent_vectors(vqvae, x, n_cycles, window=200, chunk=4096):
+    """x (n, n_cycles*window, C) -> (n, n_cycles, embedding_dim*enc_out_len): window i of every sequence through the
+    frozen VQ-VAE's patch_embed -> encoder -> vector_quantization, its z_q (B, embedding_dim, enc_out_len) flattened
+    by reshape(B, -1) (create_latent_space_dataset_VQ_VAE, latentspace_dataloader.py:144-203)."""
+    n, LT, C = x.shape
+    if LT != n_cycles * window:
+        raise ValueError(f"sequence length {LT} is not n_cycles * window = {n_cycles} * {window}")
+    rows = x.reshape(n * n_cycles, window, C)
+    out = []
+    for o in range(0, len(rows), chunk):
+        z_e = vqvae.encoder(vqvae.patch_embed(rows[o:o + chunk]))
+        z_q = vqvae.vector_quantization(z_e)[1]
+        out.append(z_q.reshape(z_q.shape[0], -1).float())
+    return torch.cat(out).view(n, n_cycles, -1)
+
+
+class ClassificationDataModule:
+    """The classification surface of ASIMoWDataModule(task="classification") / LatentPredDataModule(task=
+    "classification") (train_classification_model.py:84-101): ``splits`` = [(x (n, n_cycles*200, 2), labels (n,))]
+    for train / val / test.  dataset "asimow" feeds the windows as they are (the GRU reshapes them to
+    (B, n_cycles, 400)); "latent_vq_vae" feeds the frozen VQ-VAE's latent vectors (n, n_cycles, in_dim).  The training
+    loader samples with replacement by class weight; validation and test are sequential."""
+
+    def __init__(self, splits, batch_size=512, n_cycles=5, dataset="asimow", vqvae=None, seed=0, window=200):
+        if dataset not in ("asimow", "latent_vq_vae"):
+            raise ValueError(f"Invalid dataset name. {dataset} not supported")
+        if dataset == "latent_vq_vae" and vqvae is None:
+            raise ValueError("dataset latent_vq_vae needs the frozen VQ-VAE")
+        self.splits, self.batch_size, self.n_cycles, self.dataset = splits, batch_size, n_cycles, dataset
+        self.vqvae, self.seed, self.window = vqvae, seed, window
+        self.ds = None
+
+    @property
+    def in_dim(self):
+        """Width of one GRU time step: 200*2 raw samples, or embedding_dim * enc_out_len (utils.py:40)."""
+        if self.dataset == "asimow":
+            return self.window * 2
+        return int(self.vqvae.embedding_dim * self.vqvae.enc_out_len)
+
+    def setup(self, stage=None):
+        if self.ds is not None:
+            return
+        self.ds = []
+        for x, y in self.splits:
+            if self.dataset == "latent_vq_vae":
+                x = latent_vectors(self.vqvae, x, self.n_cycles, self.window)
+            self.ds.append((x.float(), y.long()))
+        self.train_ds, self.val_ds, self.test_ds = self.ds
+
+    def train_dataloader(self):
+        return WeightedBatches(self.train_ds, class_sampling_weights(self.train_ds[1]), self.batch_size, self.seed)
+
+    def val_dataloader(self):
+        return DeviceBatches(self.val_ds, self.batch_size, shuffle=False, rank=0, world=1)
+
+    def test_dataloader(self):
+        return DeviceBatches(self.test_ds, self.batch_size, shuffle=False, rank=0, world=1)

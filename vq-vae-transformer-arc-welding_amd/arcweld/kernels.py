@@ -762,3 +762,70 @@ def ce_bwd(logits, V, y, ignore_index, lse, count, g, dlogits, stream=None):
 
 def ce_finalize(loss_sum, count, out, stream=None):
     call("aw_ce_finalize", ptr(loss_sum), ptr(count), ptr(out), stream_ptr(stream))
+
+
+# ------------------------------------------------------------------------------ GRU recurrence
+def gru_padded(H):
+    """Hp of the GRU kernels' padded layout (include/arcweld_amd.h): H rounded up to a multiple of 32."""
+    return (int(H) + 31) // 32 * 32
+
+
+def _chk_gru(name, t, shape, dtype):
+    if t is None:
+        return
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise nat.NativeError(f"gru: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)}, got "
+                              f"{t.dtype} {tuple(t.shape)}")
+
+
+def gru_pack_weights(w_hh, H, w_fwd=None, w_bwd=None, stream=None):
+    """Zero-padded operand images of W_hh (3H, H): w_fwd [3][Hp][Hp], w_bwd [Hp][3*Hp] (either may be None)."""
+    Hp = gru_padded(H)
+    T = (w_fwd if w_fwd is not None else w_bwd).dtype
+    _chk_gru("w_hh", w_hh, (3 * H, H), torch.float32)
+    _chk_gru("w_fwd", w_fwd, (3, Hp, Hp), T)
+    _chk_gru("w_bwd", w_bwd, (Hp, 3 * Hp), T)
+    call("aw_gru_pack_weights", ptr(w_hh), int(H), dtype_code(T), ptr(w_fwd), ptr(w_bwd), stream_ptr(stream))
+
+
+def gru_step_fwd(H, T, gi, b_hh, h, saved, w_fwd=None, h_prev_op=None, h_prev=None, h_op=None, stream=None):
+    """aw_gru_step_fwd: one time step of one layer (T = the operand dtype; h_prev_op = h_prev = None: zero state)."""
+    B, Hp = gi.shape[0], gru_padded(H)
+    _chk_gru("gi", gi, (B, 3 * Hp), torch.float32)
+    _chk_gru("b_hh", b_hh, (3 * H,), torch.float32)
+    _chk_gru("h", h, (B, Hp), torch.float32)
+    _chk_gru("saved", saved, (B, 4 * Hp), torch.float32)
+    _chk_gru("h_prev_op", h_prev_op, (B, Hp), T)
+    _chk_gru("h_prev", h_prev, (B, Hp), torch.float32)
+    _chk_gru("h_op", h_op, (B, Hp), torch.bfloat16)
+    _chk_gru("w_fwd", w_fwd, (3, Hp, Hp), T)
+    call("aw_gru_step_fwd", B, int(H), dtype_code(T), ptr(h_prev_op), ptr(h_prev), ptr(w_fwd), ptr(gi), ptr(b_hh),
+         ptr(h), ptr(h_op), ptr(saved), stream_ptr(stream))
+
+
+def gru_step_bwd(H, T, saved, dh, dgi, dgh, w_bwd=None, dgh_next_op=None, dh_next=None, saved_next=None, dy=None,
+                 h_prev=None, dgi_op=None, dgh_op=None, stream=None):
+    """aw_gru_step_bwd: one time step of one layer's backward (the *_next arguments are step t+1's: all None at the
+    last step)."""
+    B, Hp = saved.shape[0], gru_padded(H)
+    f32 = torch.float32
+    _chk_gru("saved", saved, (B, 4 * Hp), f32)
+    _chk_gru("saved_next", saved_next, (B, 4 * Hp), f32)
+    for name, t in (("dh", dh), ("dh_next", dh_next), ("dy", dy), ("h_prev", h_prev)):
+        _chk_gru(name, t, (B, Hp), f32)
+    for name, t in (("dgi", dgi), ("dgh", dgh)):
+        _chk_gru(name, t, (B, 3 * Hp), f32)
+    for name, t in (("dgi_op", dgi_op), ("dgh_op", dgh_op)):
+        _chk_gru(name, t, (B, 3 * Hp), torch.bfloat16)
+    _chk_gru("dgh_next_op", dgh_next_op, (B, 3 * Hp), T)
+    _chk_gru("w_bwd", w_bwd, (Hp, 3 * Hp), T)
+    call("aw_gru_step_bwd", B, int(H), dtype_code(T), ptr(dgh_next_op), ptr(dh_next), ptr(saved_next), ptr(w_bwd),
+         ptr(dy), ptr(saved), ptr(h_prev), ptr(dh), ptr(dgi), ptr(dgh), ptr(dgi_op), ptr(dgh_op), stream_ptr(stream))
+
+
+def gru_bias_grad(dg, H, db, stream=None):
+    """aw_gru_bias_grad: db (3H) += the column sums of the f32 gate gradients dg (rows, 3*Hp)."""
+    rows = dg.shape[0]
+    _chk_gru("dg", dg, (rows, 3 * gru_padded(H)), torch.float32)
+    _chk_gru("db", db, (3 * H,), torch.float32)
+    call("aw_gru_bias_grad", ptr(dg), rows, int(H), ptr(db), stream_ptr(stream))

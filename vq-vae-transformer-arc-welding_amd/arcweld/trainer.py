@@ -290,7 +290,8 @@ class Trainer:
     @torch.no_grad()
     def evaluate(self, model, loader, stage="val"):
         """Runs validation_step/test_step over the loader; every logged scalar is averaged over the epoch
-        (weighted by batch size, Lightning's on_epoch reduction) and, under DDP, over ranks."""
+        (weighted by batch size, Lightning's on_epoch reduction) and, under DDP, over ranks.  A model that defines
+        on_validation_epoch_end / on_test_epoch_end has it called after the pass."""
         model.eval()
         dev = next(model.parameters()).device
         sums, total = {}, 0
@@ -304,14 +305,22 @@ class Trainer:
                 sums[k] = sums.get(k, 0.0) + v * bs
             total += bs
         model.train()
-        if not sums:
-            return {}
-        keys = sorted(sums)
-        vec = torch.stack([sums[k] for k in keys] + [torch.tensor(float(total), device=dev)])
-        if self.world() > 1 and stage == "val":
-            dist.all_reduce(vec)
-        vec = vec.cpu()
-        return {k: float(vec[j] / vec[-1]) for j, k in enumerate(keys)}
+        metrics = {}
+        if sums:
+            keys = sorted(sums)
+            vec = torch.stack([sums[k] for k in keys] + [torch.tensor(float(total), device=dev)])
+            if self.world() > 1 and stage == "val":
+                dist.all_reduce(vec)
+            vec = vec.cpu()
+            metrics = {k: float(vec[j] / vec[-1]) for j, k in enumerate(keys)}
+        # Lightning's epoch-end hook (model/classification_model.py logs val/f1_score_mean there): what it logs joins
+        # the returned metrics, so EarlyStopping / ModelCheckpoint can monitor it
+        hook = getattr(model, "on_validation_epoch_end" if stage == "val" else "on_test_epoch_end", None)
+        if callable(hook):
+            model._logged = {}
+            hook()
+            metrics.update({k: float(v) for k, v in model.logged.items()})
+        return metrics
 
     def validate(self, model, datamodule=None, dataloaders=None):
         if datamodule is not None:
