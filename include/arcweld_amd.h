@@ -49,7 +49,9 @@ int aw_version(void);
  *   C2 (c2_mode): 1 = act(v), 2 = v, 3 = v * dropout(drop2_seed, r*N+c, drop2_p); stored as c2_dtype;
  *   c2_mode 4: C = act(v) and C2 = act'(v) instead (from one exponential: the backward multiplies by the saved
  *   derivative, act = AW_ACT_DERIV, rather than evaluating act' of a saved pre-activation)
- *   colstats (f64, 2*stats_mod): += v and v*v into slot (c % stats_mod)      (BatchNorm batch statistics)
+ *   colstats (f64, 2*stats_mod): += v and v*v into slot (c % stats_mod)      (BatchNorm batch statistics; the
+ *   specialised bias + bias_mod + colstats epilogues sum the f32 v in f64 throughout -- no f32 summation order, so any
+ *   row grouping gives the same sums to f64 rounding --, the generic kernel sums f32 partials of a tile's rows)
  *   a_rowsum (f32, M): += sum_k A[m][k]                                      (bias gradients, fused)
  */
 typedef struct {
@@ -169,8 +171,18 @@ int aw_wgrad_set_spin_limit(int polls);
  *   erf form of aw_gemm's bf16 epilogues); drop_masks (drop_p > 0) = what the forward wrote.
  * All activations are [N][H] bf16 with row stride H, 16-B aligned; N * H * 2 < 2^31; 1 <= R <= AW_RES_CHAIN_MAX;
  * taps = 3 needs seg = 16 and N % 16 == 0.  drop_seed / seed_ptr select the masks (forward); store_policy AW_STORE_WT
- * (sc1) or AW_STORE_NT for every global store. */
+ * (sc1) or AW_STORE_NT for every global store.
+ * Forward tail (taps = 3 only, tail_k1 = 1 .. AW_RES_TAIL_MAX; all-zero tail fields = no tail): the un-patch
+ * ConvTranspose1d(H -> H, kernel = stride = tail_k1) that follows the decoder stack, run on x_R while it is still in
+ * LDS: for tap j < tail_k1
+ *   tail_y[row][j * H + c] = bf16(x_R[row] . W_j[c] + tail_bias[c])          (tail_y: [N][tail_k1 * H] bf16)
+ * with tail_w[j] the forward copy of the [out][in] matrix W_j packed as a taps = 1 matrix (aw_res_pack_weights_mixed),
+ * and tail_colstats (f64, 2 * H, may be NULL) += the column sums of v and v * v over the rows < N and the tail_k1
+ * taps, from the f32 values before the bf16 rounding -- what aw_gemm with bias_mod = stats_mod = H computes on
+ * a[R-1] and the [tail_k1 * H][H] operand copy, without the launch and without reading x_R back.  a[R-1] is still
+ * stored.  (N + 64) * tail_k1 * H * 2 < 2^31; tail_y 16-B aligned. */
 #define AW_RES_CHAIN_MAX 16
+#define AW_RES_TAIL_MAX 8
 typedef struct {
   int64_t N;
   int H, R;
@@ -190,6 +202,11 @@ typedef struct {
   const uint64_t* seed_ptr;
   int store_policy;
   uint64_t* drop_masks;
+  int tail_k1;
+  const void* tail_w[AW_RES_TAIL_MAX];
+  const float* tail_bias;
+  void* tail_y;
+  double* tail_colstats;
 } aw_res_chain_fwd_args;
 typedef struct {
   int64_t N;
@@ -225,6 +242,11 @@ int aw_res_dropout_masks(int64_t N, int R, float drop_p, const uint64_t* drop_se
  * fragment as one contiguous KB. */
 #define AW_RES_PACK_MAX 32
 int aw_res_pack_weights(const void* const* src, void* const* fwd, void* const* bwd, int n, int taps, void* stream);
+/* The same launch with a tap count per job: job_taps[i] is `taps` or 1 (NULL: all `taps`).  A 1-tap job packs a
+ * [512][512] matrix beside the launch's [512][taps * 512] ones -- the chain tail's matrices ride in the decoder's
+ * forward pack launch. */
+int aw_res_pack_weights_mixed(const void* const* src, void* const* fwd, void* const* bwd, const int* job_taps, int n,
+                              int taps, void* stream);
 
 /* -------------------------------------------------------------------------------- vector quantizer
  * VectorQuantizer.forward (model/vector_quantizer.py:76-119), fp32, codebook staged in LDS, no MFMA:

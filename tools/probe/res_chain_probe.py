@@ -2,7 +2,10 @@
 dropout 0.1): time per launch of aw_res_chain_fwd / aw_res_chain_bwd against the 2R per-conv aw_gemm launches each
 replaces (the same epilogues), HIP events around `iters` launches after 3 warm-up ones; taps 1 = the encoder stack,
 3 = the decoder's k = 3 stack.
-usage on the GPU box: python tools/probe/res_chain_probe.py [iters] [taps]"""
+usage on the GPU box: python tools/probe/res_chain_probe.py [iters] [taps]
+--tail: the decoder forward chain (taps 3) with and without the un-patch ConvT as its tail (k1 = 5), beside the ConvT's
+own GEMM launch (colstats epilogue) and the pack launch with and without the five tail matrices:
+python tools/probe/res_chain_probe.py --tail [iters]"""
 import os
 import sys
 
@@ -10,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 
 
-def main(iters=20, taps=1, N=16384):
+def main(iters=20, taps=1, N=16384, tail=False):
     import torch
     sys.path.insert(0, os.path.join(REPO, "vq-vae-transformer-arc-welding_amd"))
     from arcweld import kernels as K
@@ -82,6 +85,34 @@ def main(iters=20, taps=1, N=16384):
         return t0.elapsed_time(t1) * 1000.0 / iters
 
     fl = 4.0 * R * N * H * H * (1 if taps == 1 else 3 - 2 / 16)
+    if tail:
+        k1 = 5
+        Wt, tb = rnd(k1 * H, H, sc=0.04), rnd(H, dt=torch.float32)
+        Y = torch.empty(N, k1 * H, device="cuda", dtype=BF)
+        cst = torch.zeros(2 * H, device="cuda", dtype=torch.float64)
+        tsrc = [Wt[j * H:(j + 1) * H] for j in range(k1)]
+        tpk = [torch.empty(H, H, device="cuda", dtype=BF) for _ in range(k1)]
+        K.res_pack_weights(w1 + w2 + tsrc, pk + tpk, None, taps=3, job_taps=[3] * (2 * R) + [1] * k1)
+
+        def chain_tail():
+            K.res_chain_fwd(a0, x0, pk[:R], pk[R:], b1, b2, h, a1, x, a, drop=(p, seeds), seed_ptr=ctr, masks=masks,
+                            taps=3, tail=(tpk, tb, Y, cst))
+
+        def convt_gemm():
+            K.gemm(a[R - 1], Wt, N, k1 * H, H, bias=tb, bias_mod=H, C=Y, colstats=cst, stats_mod=H)
+
+        def pack_fwd():
+            K.res_pack_weights(w1 + w2, pk, None, taps=3)
+
+        def pack_fwd_tail():
+            K.res_pack_weights(w1 + w2 + tsrc, pk + tpk, None, taps=3, job_taps=[3] * (2 * R) + [1] * k1)
+
+        with K.store_policy(1):
+            for name, fn in (("chain_fwd", chain_fwd), ("chain_tail", chain_tail), ("convt_gemm", convt_gemm),
+                             ("chain_fwd", chain_fwd), ("chain_tail", chain_tail), ("convt_gemm", convt_gemm),
+                             ("pack_fwd", pack_fwd), ("pack_fwd_tail", pack_fwd_tail)):
+                print(f"{name:14s} {timeit(fn):8.1f} us", flush=True)
+        return
     from arcweld import vqvae  # noqa: F401
     print(f"taps {taps}", flush=True)
     with K.store_policy(1):
@@ -93,4 +124,7 @@ def main(iters=20, taps=1, N=16384):
 
 
 if __name__ == "__main__":
-    main(*(int(v) for v in sys.argv[1:]))
+    if "--tail" in sys.argv[1:]:
+        main(*(int(v) for v in sys.argv[1:] if v != "--tail"), taps=3, tail=True)
+    else:
+        main(*(int(v) for v in sys.argv[1:]))

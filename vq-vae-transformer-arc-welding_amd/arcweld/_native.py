@@ -69,6 +69,7 @@ OPS_PER_SEG = 2     # AW_OPS_PER_SEG
 
 RES_CHAIN_MAX = 16  # AW_RES_CHAIN_MAX
 RES_PACK_MAX = 32   # AW_RES_PACK_MAX
+RES_TAIL_MAX = 8    # AW_RES_TAIL_MAX
 _E = RES_CHAIN_MAX
 
 
@@ -78,7 +79,9 @@ class ResChainFwdArgs(ctypes.Structure):
                 ("w1", c_p * _E), ("w2", c_p * _E), ("b1", c_p * _E), ("b2", c_p * _E),
                 ("dgelu_h", c_p * _E), ("a1", c_p * _E), ("dgelu_x", c_p * _E), ("a", c_p * _E),
                 ("drop_p", c_f), ("drop_seed", ctypes.c_uint64 * _E), ("seed_ptr", c_p), ("store_policy", c_int),
-                ("drop_masks", c_p)]
+                ("drop_masks", c_p),
+                ("tail_k1", c_int), ("tail_w", c_p * RES_TAIL_MAX), ("tail_bias", c_p), ("tail_y", c_p),
+                ("tail_colstats", c_p)]
 
 
 class ResChainBwdArgs(ctypes.Structure):
@@ -105,6 +108,8 @@ SIGNATURES = {
     "aw_res_chain_fwd": [ctypes.POINTER(ResChainFwdArgs), c_p],
     "aw_res_chain_bwd": [ctypes.POINTER(ResChainBwdArgs), c_p],
     "aw_res_pack_weights": [ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(c_p), c_int, c_int, c_p],
+    "aw_res_pack_weights_mixed": [ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(c_p),
+                                  ctypes.POINTER(c_int), c_int, c_int, c_p],
     "aw_res_dropout_masks_bytes": [c_i64, c_int],
     "aw_res_dropout_masks": [c_i64, c_int, c_f, ctypes.POINTER(ctypes.c_uint64), c_p, c_p, c_p],
     "aw_weight_relayout_batch": [ctypes.POINTER(RelayoutJob), c_int, c_int, c_p],

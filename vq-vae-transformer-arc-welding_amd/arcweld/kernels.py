@@ -301,14 +301,25 @@ def _chain_flops(R, N, H, taps, seg):
     return 4.0 * R * N * H * H * (3 - 2.0 / seg)
 
 
+def convt_tail_ok():
+    """The decoder chain may run the un-patch ConvT as its tail (res_chain_fwd(tail=...)).  ARCWELD_CONVT_TAIL=0 keeps
+    the ConvT's own GEMM launch (A/B runs, and the tests that compare the two)."""
+    import os
+    return os.environ.get("ARCWELD_CONVT_TAIL", "1") != "0"
+
+
 def res_chain_fwd(a0, x0, w1, w2, b1, b2, dh, a1, dx, a, drop=(0.0, None), seed_ptr=None, masks=None, taps=1, seg=16,
-                  stream=None):
+                  stream=None, tail=None):
     """One aw_res_chain_fwd launch over the R = len(w1) ResBlocks (see include/arcweld_amd.h).
 
     a0 / x0: (N, H) bf16; w1 / w2: R packed weight copies (res_pack_weights); b1 / b2: R f32 biases; dh / a1 / dx / a:
     R output tensors each -- dh[r] = GELU'(h_r), a1[r], dx[r] = GELU'(x_{r+1}) (the backward's multipliers), a[r]
     (dh, a1, dx entries may be None: not stored; dx[R-1] is never stored); drop = (p, R seeds); masks: None or a
-    res_dropout_masks_empty(N, R) buffer the launch fills with the keep bits (for res_chain_bwd)."""
+    res_dropout_masks_empty(N, R) buffer the launch fills with the keep bits (for res_chain_bwd).
+
+    tail (taps 3 only) = (wt, bias, Y, colstats): the un-patch ConvT on x_R inside the launch -- wt: its k1 matrices
+    [out][in], each packed as a 1-tap forward copy (res_pack_weights(..., job_taps=)), bias: (H,) f32, Y: (N, k1 H)
+    bf16, colstats: (2 H,) f64 accumulators or None."""
     N, H = a0.shape
     R = len(w1)
     if not (1 <= R <= RES_CHAIN_MAX) or not all(len(v) == R for v in (w2, b1, b2, dh, a1, dx, a)):
@@ -325,11 +336,33 @@ def res_chain_fwd(a0, x0, w1, w2, b1, b2, dh, a1, dx, a, drop=(0.0, None), seed_
     g.seed_ptr = ptr(seed_ptr)
     g.store_policy = _chain_store_policy()
     g.drop_masks = ptr(masks)
-    _maybe_timed(stream, "gemm_bf16", _chain_flops(R, N, H, taps, seg),
+    flops, extra = _chain_flops(R, N, H, taps, seg), []
+    if tail is not None:
+        wt, tb, Y, cst = tail
+        k1 = len(wt)
+        if taps != 3 or not (1 <= k1 <= nat.RES_TAIL_MAX):
+            raise nat.NativeError(f"res_chain_fwd: the tail needs taps == 3 and 1..{nat.RES_TAIL_MAX} matrices")
+        if Y.dtype != torch.bfloat16 or tuple(Y.shape) != (N, k1 * H) or not Y.is_contiguous():
+            raise nat.NativeError(f"res_chain_fwd: tail Y must be a contiguous ({N}, {k1 * H}) bfloat16 tensor")
+        if tb.dtype != torch.float32 or tb.numel() != H or not tb.is_contiguous():
+            raise nat.NativeError("res_chain_fwd: tail bias must be (H,) float32")
+        if cst is not None and (cst.dtype != torch.float64 or cst.numel() < 2 * H or not cst.is_contiguous()):
+            raise nat.NativeError("res_chain_fwd: tail colstats must be (2 H,) float64")
+        for w in wt:
+            if w.dtype != torch.bfloat16 or w.numel() != H * H or not w.is_contiguous():
+                raise nat.NativeError("res_chain_fwd: tail matrices must be packed (H, H) bfloat16 copies")
+        g.tail_k1 = k1
+        for j in range(k1):
+            g.tail_w[j] = ptr(wt[j])
+        g.tail_bias, g.tail_y, g.tail_colstats = ptr(tb), ptr(Y), ptr(cst)
+        # the launch's record carries the ConvT it absorbed: its algorithmic flops, and Y and the matrices as bytes
+        flops += 2.0 * N * k1 * H * H
+        extra = [Y, tb] + list(wt)
+    _maybe_timed(stream, "gemm_bf16", flops,
                  lambda sp: call("aw_res_chain_fwd", ctypes.byref(g), sp),
                  lambda: (f"res_chain_fwd_kernel<{int(taps)}>",
                           _nbytes([a0, x0, masks] + list(w1) + list(w2) + list(b1) + list(b2) + list(dh) + list(a1) +
-                                  list(dx)[:-1] + list(a))))
+                                  list(dx)[:-1] + list(a) + extra)))
 
 
 def res_chain_bwd(gx, gxo, w1t, w2t, dh, x0, dx, gh, gxo_out, drop_p=0.0, masks=None, taps=1, seg=16, stream=None):
@@ -359,23 +392,30 @@ def res_chain_bwd(gx, gxo, w1t, w2t, dh, x0, dx, gh, gxo_out, drop_p=0.0, masks=
                                   list(gxo_out))))
 
 
-def res_pack_weights(src, fwd=None, bwd=None, taps=1, stream=None):
+def res_pack_weights(src, fwd=None, bwd=None, taps=1, stream=None, job_taps=None):
     """Fragment-packed copies of [512][taps*512] bf16 [out][(tap, in)] weights for the chain (aw_res_pack_weights):
     fwd[i] <- W packed (aw_res_chain_fwd's w1 / w2), bwd[i] <- the backward operand packed (aw_res_chain_bwd's w1t /
-    w2t); either list may be None.  One launch per 32 matrices."""
+    w2t); either list may be None.  One launch per 32 matrices.  job_taps[i] (default taps) may be 1 in a taps = 3
+    launch: a [512][512] matrix, forward copy only (the chain tail's matrices, aw_res_pack_weights_mixed)."""
     n = len(src)
     fwd = fwd if fwd is not None else [None] * n
     bwd = bwd if bwd is not None else [None] * n
-    if len(fwd) != n or len(bwd) != n:
+    jt = [int(taps)] * n if job_taps is None else [int(v) for v in job_taps]
+    if len(fwd) != n or len(bwd) != n or len(jt) != n:
         raise nat.NativeError("res_pack_weights: list lengths differ")
-    for t in list(src) + [t for t in fwd + bwd if t is not None]:
-        if t.dtype != torch.bfloat16 or t.numel() != 512 * 512 * taps or not t.is_contiguous():
-            raise nat.NativeError(f"res_pack_weights: need contiguous 512 x {512 * taps} bfloat16 tensors")
+    for i in range(n):
+        for t in (src[i], fwd[i], bwd[i]):
+            if t is not None and (t.dtype != torch.bfloat16 or t.numel() != 512 * 512 * jt[i] or not t.is_contiguous()):
+                raise nat.NativeError(f"res_pack_weights: need contiguous 512 x {512 * jt[i]} bfloat16 tensors")
     for c0 in range(0, n, nat.RES_PACK_MAX):
         sl = slice(c0, c0 + nat.RES_PACK_MAX)
         m = len(src[sl])
         arr = lambda ts: (ctypes.c_void_p * m)(*[ptr(t) for t in ts])  # noqa: E731
-        call("aw_res_pack_weights", arr(src[sl]), arr(fwd[sl]), arr(bwd[sl]), m, int(taps), stream_ptr(stream))
+        if job_taps is None:
+            call("aw_res_pack_weights", arr(src[sl]), arr(fwd[sl]), arr(bwd[sl]), m, int(taps), stream_ptr(stream))
+        else:
+            call("aw_res_pack_weights_mixed", arr(src[sl]), arr(fwd[sl]), arr(bwd[sl]), (ctypes.c_int * m)(*jt[sl]), m,
+                 int(taps), stream_ptr(stream))
 
 
 # ------------------------------------------------------------------------------------------------ VQ

@@ -171,10 +171,11 @@ def _bn_block_bwd(sv, r, gy, w1d, w2d, grads, bns, slot, wgrads, need_copy):
     return gx, gxo
 
 
-def _chain_fwd(sv, weights, biases, RT, save):
+def _chain_fwd(sv, weights, biases, RT, save, tail=None):
     """Forward of the whole stack through aw_res_chain_fwd, from sv.xs[0] / sv.a0s[0].  Fills sv with GELU'(h), a1,
     GELU'(x), a per block -- a1 and a as the per-conv route makes them, the saved derivatives in place of its h and x
-    (None without `save`) --, the operand copies the backward packs its weights from and the dropout keep bits."""
+    (None without `save`) --, the operand copies the backward packs its weights from and the dropout keep bits.
+    tail: see ``forward``; its matrices are packed in the same launch as the stack's."""
     geo = sv.geo
     R, H, taps, T = len(biases), geo.H, geo.taps, sv.T
     x0, a0 = sv.xs[0], sv.a0s[0]
@@ -189,14 +190,23 @@ def _chain_fwd(sv, weights, biases, RT, save):
     # chain starts reading
     wsrc = [w for r in range(R) for w in weights[r]]
     pk = [torch.empty(H, geo.Kd, device=dev, dtype=T) for _ in wsrc]
-    K.res_pack_weights(wsrc, pk, None, taps=taps)
+    ktail = None
+    if tail is not None:
+        Wt, tb, Y, cst = tail
+        k1 = Wt.shape[0] // H
+        tsrc = [Wt[j * H:(j + 1) * H] for j in range(k1)]      # k1 contiguous [out][in] matrices
+        tpk = [torch.empty(H, H, device=dev, dtype=T) for _ in tsrc]
+        K.res_pack_weights(wsrc + tsrc, pk + tpk, None, taps=taps, job_taps=[taps] * len(wsrc) + [1] * k1)
+        ktail = (tpk, tb, Y, cst)
+    else:
+        K.res_pack_weights(wsrc, pk, None, taps=taps)
     if save:
         sv.pk_bwd = wsrc               # the sources of the backward's packed copies
         if sv.p_drop > 0 and R > 1:
             sv.masks = K.res_dropout_masks_empty(N, R, dev)
     K.res_chain_fwd(a0, x0, pk[0::2], pk[1::2], [b1 for b1, _ in biases], [b2 for _, b2 in biases], sv.hs, sv.a1s,
                     sv.xs[1:], sv.a0s[1:], drop=(sv.p_drop, sv.seeds), seed_ptr=sv.ctr, masks=sv.masks, taps=taps,
-                    seg=geo.S)
+                    seg=geo.S, tail=ktail)
 
 
 def _chain_bwd(sv, gx, gxo, grads):
@@ -222,7 +232,7 @@ def _chain_bwd(sv, gx, gxo, grads):
 
 
 def forward(geo, x0, a0, weights, biases, bns=None, *, T, RT, p_drop=0.0, seeds=None, ctr=None, training=False,
-            chain=False, last_operand_only=True, in_place=False, save=True):
+            chain=False, last_operand_only=True, in_place=False, save=True, tail=None):
     """R = len(biases) ResBlocks from x0 [N][H] (dtype RT) and a0 = GELU(x0) (operand dtype T).
 
     weights[r]: block r's (conv1, conv2) forward operands [H][Kd]; biases[r]: its (b1, b2); bns: per block the
@@ -231,7 +241,10 @@ def forward(geo, x0, a0, weights, biases, bns=None, *, T, RT, p_drop=0.0, seeds=
     asked K.res_chain_ok; never with BatchNorm).  last_operand_only: the last block writes only the operand copy of
     x_R itself (what the next conv consumes: no f32 x_R, no GELU); otherwise it is a block like any other.  in_place
     (nothing saved): x and a are updated in place and h / a1 reused across blocks.  save=False keeps no per-block
-    tensor (and the chain stores none of its derivatives).
+    tensor (and the chain stores none of its derivatives).  tail = (Wt [k1 H][H] operand copy, bias (H,) f32,
+    Y (N, k1 H) bf16, colstats (2 H,) f64 or None): only on the chain route of a taps = 3 stack -- the chain launch
+    also runs the un-patch ConvT on x_R (Y and the BatchNorm column statistics of K.gemm(x_R, Wt, bias_mod=H,
+    stats_mod=H)).
 
     Returns (x_R or None when only its operand copy was written, the operand copy -- GELU(x_R), or x_R itself under
     last_operand_only --, Saved)."""
@@ -241,8 +254,10 @@ def forward(geo, x0, a0, weights, biases, bns=None, *, T, RT, p_drop=0.0, seeds=
     route = "bn" if bns is not None else "chain" if chain else "conv"
     sv = Saved(geo, route, T, p_drop, seeds, ctr, training, x0, a0)
     e = lambda dt: torch.empty(N, H, device=dev, dtype=dt)  # noqa: E731
+    if tail is not None and (route != "chain" or geo.taps != 3):
+        raise ValueError("resstack.forward: the ConvT tail runs only inside the decoder chain")
     if route == "chain":
-        _chain_fwd(sv, weights, biases, RT, save)
+        _chain_fwd(sv, weights, biases, RT, save, tail)
         return sv.xs[R], sv.a0s[R], sv
     x, a, h, a1 = x0, a0, None, None
     for r in range(R):

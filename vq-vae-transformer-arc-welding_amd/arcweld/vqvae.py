@@ -243,14 +243,6 @@ def forward(m, x, training: bool, need_backward: bool, dtype=None, seed: int = 0
     # ---- decoder: 1x1 conv + ResBlocks with k=3 convs along the window
     y0, ya0 = e(N, H, dt=RT), e(N, H, dt=T)
     K.gemm(zq_T, Wd0, N, H, D, bias=pr["dec0"].bias, C=y0, C2=ya0, c2_mode=1)
-    _, yR_T, sv.dec = resstack.forward(resstack.Geometry(3, H, S), y0, ya0, dec_w, _biases(pr["dec"]), pr["dec_bn"],
-                                       seeds=[_mix(seed, 200 + r) for r in range(R)],
-                                       chain=K.res_chain_ok(H, R, T, RT, 3, S, "DEC"), **stack)
-    if R == 0:
-        yR_T = _operand(y0, T)
-
-    # ---- un-patch: ConvT(H->H, k1) with BN statistics in the epilogue, then the fused head
-    bn = pr["bn"]
     # In the bf16 operand mode the ConvT output Y is bf16 (what autocast keeps for a ConvTranspose1d output; the BN
     # statistics still come from the f32 values in the epilogue): half the bytes of the GEMM's output and of the head's
     # passes over Y.  Round 3 measured it even over the step (the head passes are VALU-bound); on the round-4 step it
@@ -259,7 +251,20 @@ def forward(m, x, training: bool, need_backward: bool, dtype=None, seed: int = 0
     bf_y = T != F32 and K.head_bf16_ok(H) and os.environ.get("ARCWELD_HEAD_BF16", "1") == "1"
     Y = e(N, k1 * H, dt=T if bf_y else F32)
     colstats = acc["colstats"] if training else None
-    K.gemm(yR_T, Wt1, N, k1 * H, H, bias=pr["t1"].bias, bias_mod=H, C=Y, colstats=colstats, stats_mod=H)
+    # The un-patch ConvT rides as the tail of the decoder chain launch when that runs and Y is bf16: x_R is still in
+    # LDS there, so the ConvT is k1 more 1-tap convs and no launch of its own (ARCWELD_CONVT_TAIL=0: the GEMM below)
+    dec_chain = K.res_chain_ok(H, R, T, RT, 3, S, "DEC") and pr["dec_bn"] is None
+    convt_tail = dec_chain and bf_y and k1 <= nat.RES_TAIL_MAX and K.convt_tail_ok()
+    _, yR_T, sv.dec = resstack.forward(resstack.Geometry(3, H, S), y0, ya0, dec_w, _biases(pr["dec"]), pr["dec_bn"],
+                                       seeds=[_mix(seed, 200 + r) for r in range(R)], chain=dec_chain,
+                                       tail=(Wt1, pr["t1"].bias, Y, colstats) if convt_tail else None, **stack)
+    if R == 0:
+        yR_T = _operand(y0, T)
+
+    # ---- un-patch: ConvT(H->H, k1) with BN statistics in the epilogue, then the fused head
+    bn = pr["bn"]
+    if not convt_tail:
+        K.gemm(yR_T, Wt1, N, k1 * H, H, bias=pr["t1"].bias, bias_mod=H, C=Y, colstats=colstats, stats_mod=H)
     stats = e(4 * H)
     K.bn_finalize(colstats, N * k1, H, bn.weight, bn.bias, bn.running_mean, bn.running_var,
                   bn.num_batches_tracked if training else None, bn.eps,

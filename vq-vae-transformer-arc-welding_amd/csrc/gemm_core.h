@@ -21,6 +21,7 @@
 // (act / copy / dropout-masked copy), BatchNorm column statistics; fused A-row sums (bias gradients) from the
 // A fragments in registers.
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 // The LDS-DMA inline asm writes M0 (declared as clobbered).  No compiler-generated code in these kernels uses M0
@@ -730,7 +731,14 @@ __global__ __launch_bounds__(Cfg<BMT>::NTH, RAGGED ? 1 : Cfg<BMT>::MINB) void ge
   const int col = n0 + c4;
   // specialised codes are issued only when every operand row is 16-B aligned and N % 4 == 0
   const bool vec = GEN ? (P.vec && col + 4 <= N) : (col < N);
-  float bias[4], csum[4] = {0.f, 0.f, 0.f, 0.f}, csq[4] = {0.f, 0.f, 0.f, 0.f};
+  // The specialised codes sum the column statistics in f64 from the first add on: the decoder chain's ConvT tail
+  // (reschain.hip) sums the same values over other row groups, and the two meet only if neither carries an f32
+  // summation order -- their BatchNorm mean / invstd then round to the same f32 (tests/test_res_chain.py compares
+  // x_hat bit for bit).  EP_GENERIC keeps its f32 partials of 16 and 128 rows: within its 128-VGPR budget the eight
+  // doubles took its scratch from 40 to 120 B per lane, for every generic launch, with or without statistics.
+  using stat_t = std::conditional_t<GEN, float, double>;
+  float bias[4];
+  stat_t csum[4] = {0, 0, 0, 0}, csq[4] = {0, 0, 0, 0};
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int c = col + e;
@@ -816,8 +824,9 @@ __global__ __launch_bounds__(Cfg<BMT>::NTH, RAGGED ? 1 : Cfg<BMT>::MINB) void ge
           else if (c2m == 3) y = x * ds2[e];
           w[e] = y;
           if (f_stats && col + e < N) {
-            csum[e] += x;
-            csq[e] += x * x;
+            const stat_t xs = (stat_t)x;
+            csum[e] += xs;
+            csq[e] += xs * xs;
           }
         }
         if (FASTGELU && c2m == 1 && !f_tanh) aw_gelu4(v, w);
@@ -861,7 +870,7 @@ __global__ __launch_bounds__(Cfg<BMT>::NTH, RAGGED ? 1 : Cfg<BMT>::MINB) void ge
   AW_STAMP(4);
   if (f_stats) {  // BatchNorm batch statistics: reduce the NR row-groups of a column, one f64 atomic each
     __syncthreads();
-    float* red = Cs;   // [NR][2][128]
+    stat_t* red = reinterpret_cast<stat_t*>(Cs);   // [NR][2][128]
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       red[(r0 * 2 + 0) * 128 + c4 + e] = csum[e];
@@ -869,7 +878,7 @@ __global__ __launch_bounds__(Cfg<BMT>::NTH, RAGGED ? 1 : Cfg<BMT>::MINB) void ge
     }
     __syncthreads();
     if (tid < 128 && n0 + tid < N) {
-      float a = 0.f, b = 0.f;
+      stat_t a = 0, b = 0;
 #pragma unroll
       for (int g = 0; g < NR; ++g) {
         a += red[(g * 2 + 0) * 128 + tid];

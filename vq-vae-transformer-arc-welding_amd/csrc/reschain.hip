@@ -42,6 +42,10 @@
 //  * the residual stream (x forward, gx backward) stays in registers as bf16 (the bf16 mode's resid dtype); the
 //    weight gradients' operands are written as the unfused path writes them (a1, a forward; gh and the masked gx
 //    backward), and in place of the unfused path's h and x the forward saves GELU'(h), GELU'(x') for the backward.
+//  * the decoder's forward chain may go on past the last block (TAIL): the un-patch ConvTranspose1d(H -> H, k1) that
+//    consumes x_R is k1 independent 1-tap convs over the image x_R was just staged in, so it runs there, with its
+//    bias, bf16 output Y [N][k1 H] and BatchNorm column statistics, instead of as a GEMM launch of its own
+//    (model/vq_vae_patch_embedd.py reverse_patch_embed.proj[0]).
 // Per element the epilogues run the unfused GEMM epilogue's operations in its order (gemm_core.h), and each
 // accumulator sees the same MFMA sequence (K ascending in 32-deep steps, tap-major as the implicit conv GEMM), so
 // the forward's outputs a1 / a / keep bits are the unfused path's bit for bit; the saved derivatives are GELU' of the
@@ -74,6 +78,8 @@ template <int TAPS> struct EcGeo {
   static constexpr int FLAGS = SCR + 8 * EC_SCR;                   // 8 per-wave "epilogues done" counters
   static constexpr int BIAS = FLAGS + 64;                          // per-wave bias slot (the current conv's 64)
   static constexpr int LDS = BIAS + 8 * 256;
+  static constexpr int TBIAS = LDS;                                // the ConvT tail's bias, per wave as BIAS
+  static constexpr int LDS_TAIL = TBIAS + 8 * 256;
   static constexpr uint32_t WBYTES = (uint32_t)EC_H * EC_H * 2 * TAPS;   // one packed weight matrix
   static constexpr int WWAVE = 4 * KS * 1024;                      // a wave's 4 packed block rows
   // Image swizzle key of token u of a 16-token group: chunk c of the token sits at chunk c ^ key(u).  Three kinds of
@@ -87,7 +93,7 @@ template <int TAPS> struct EcGeo {
   static constexpr uint64_t KEYS = TAPS == 1 ? 0xfe76dc54ba329810ull : 0xf53ac739685ace10ull;
   __device__ static int key(int u) { return u < 0 ? 15 : u > 15 ? 0 : (int)((KEYS >> (4 * u)) & 15); }
 };
-static_assert(EcGeo<3>::LDS <= 160 * 1024, "decoder chain LDS");
+static_assert(EcGeo<3>::LDS_TAIL <= 160 * 1024, "decoder chain LDS");
 
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 __device__ __forceinline__ rsrc_t ec_rsrc(const void* p, uint32_t nbytes) {
@@ -253,10 +259,58 @@ __device__ __forceinline__ void ec_scales(u32x2 keep, int i, int j, float k, flo
 // the next conv's weights (rn, when has_next).  Image reads of step s = 16 t + 4a + b (tap t): token 16j + li + d_t,
 // chunk 4(4a + b) + g lives at (rb[t] ^ 64 b) + 256 a + JS j + io.  Step 2v of tap 0 waits for flag v >= target
 // (another wave's slice).  step(s) runs behind step s's MFMAs, tail() behind the last K step's weight loads.
+// The general form walks KS steps of a matrix packed with KS steps per block row: all of G's taps (KS = G::KS), or
+// only the centre tap of a TAPS = 3 image with a 1-tap matrix (KS = 16: the ConvT tail).  The next matrix may be
+// packed with another step count: its lane offset is wln and its block rows are nks steps long (the last decoder
+// conv prefetches the first 1-tap tail matrix).  MAYSKIP: target < 0 waits for no slice (the image is complete).
+template <class G, int KS, bool MAYSKIP, typename Tail, typename Step>
+__device__ __forceinline__ void ec_conv_g(f32x4 (&acc)[4][4], uint4 (&wf)[2][4], char* smem,
+                                          const int (&rb)[G::KS / 16], int io, rsrc_t rc, rsrc_t rn, bool has_next,
+                                          int wl, int wln, int nks, int w, int target, Tail tail, Step step) {
+  constexpr int T = G::KS / 16, T0 = KS == G::KS ? 0 : T / 2;
+  static_assert(KS == G::KS || KS == 16, "all taps or the centre tap");
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  int rbi[T];
+#pragma unroll
+  for (int t = 0; t < T; ++t) rbi[t] = rb[t] + io;
+#pragma unroll
+  for (int s = 0; s < KS; ++s) {
+    const int t = T0 + (s >> 4), kk = s & 15;
+    // image fragments of step s (a wave's partner on the SIMD covers their latency): read at the step, not one
+    // ahead -- the 16 registers of a second set made the masked (dropout) kernels spill
+    if (s < 16 && (kk & 1) == 0 && (kk >> 1) != w && (!MAYSKIP || target >= 0)) ec_wait<G>(smem, kk >> 1, target);
+    uint4 bf[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bf[j] = ec_lds_r16(smem, (rbi[t] ^ (64 * (kk & 3))) + (kk >> 2) * 256 + j * G::JS);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[s & 1][i]),
+                                                            __builtin_bit_cast(bf16x8, bf[j]), acc[i][j], 0, 0, 0);
+    if (s + 2 < KS) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) wf[s & 1][i] = ec_wload(rc, wl, (i * KS + s + 2) * 1024);
+    } else if (has_next) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) wf[s & 1][i] = ec_wload(rn, wln, (i * nks + s + 2 - KS) * 1024);
+    }
+    step(s);
+    if (s == KS - 1) tail();
+    // one scheduling region per K step: the prefetch stays two steps ahead (left alone, the scheduler sinks each
+    // load down to its MFMA and waits for it there)
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
 template <class G, typename Tail, typename Step>
 __device__ __forceinline__ void ec_conv(f32x4 (&acc)[4][4], uint4 (&wf)[2][4], char* smem, const int (&rb)[G::KS / 16],
                                         int io, rsrc_t rc, rsrc_t rn, bool has_next, int wl, int w, int target,
                                         Tail tail, Step step) {
+  // (written out, not a call of ec_conv_g: routed through it the backward decoder chain came out of the register
+  // allocator with 256 VGPRs and 8 B of scratch instead of 254 and none)
   constexpr int T = G::KS / 16;
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -268,8 +322,6 @@ __device__ __forceinline__ void ec_conv(f32x4 (&acc)[4][4], uint4 (&wf)[2][4], c
 #pragma unroll
   for (int s = 0; s < G::KS; ++s) {
     const int t = s >> 4, kk = s & 15;
-    // image fragments of step s (a wave's partner on the SIMD covers their latency): read at the step, not one
-    // ahead -- the 16 registers of a second set made the masked (dropout) kernels spill
     if (t == 0 && (kk & 1) == 0 && (kk >> 1) != w) ec_wait<G>(smem, kk >> 1, target);
     uint4 bf[4];
 #pragma unroll
@@ -289,8 +341,6 @@ __device__ __forceinline__ void ec_conv(f32x4 (&acc)[4][4], uint4 (&wf)[2][4], c
     }
     step(s);
     if (s == G::KS - 1) tail();
-    // one scheduling region per K step: the prefetch stays two steps ahead (left alone, the scheduler sinks each
-    // load down to its MFMA and waits for it there)
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -367,14 +417,24 @@ __device__ __forceinline__ void ec_store_scratch(const char* smem, int j, const 
   for (int q = 0; q < 2; ++q) ec_store16<WT>(r, S.gs, 8192 * (2 * j + q), ec_lds_r16(smem, S.srq(q)));
 }
 
+// the same for a tensor with another row stride: the 8-token step is st8 bytes, co the column offset in bytes
+template <class G, bool WT>
+__device__ __forceinline__ void ec_store_scratch_at(const char* smem, int j, const EcStore<G>& S, rsrc_t r,
+                                                    uint32_t gs, int st8, int co) {
+#pragma unroll
+  for (int q = 0; q < 2; ++q) ec_store16<WT>(r, gs, st8 * (2 * j + q) + co, ec_lds_r16(smem, S.srq(q)));
+}
+
 template <class G> __device__ __forceinline__ void ec_init(char* smem, int tid) {
   if (tid < 8) *ec_flag<G>(smem, tid) = 0;
 }
 
-template <int TAPS, bool DROP, bool WT>
+// TAIL (TAPS = 3): the un-patch ConvT as tail_k1 more convs over the last image (see the end of the kernel)
+template <int TAPS, bool DROP, bool WT, bool TAIL>
 __global__ __launch_bounds__(EC_NTH) void res_chain_fwd_kernel(aw_res_chain_fwd_args P) {
   using G = EcGeo<TAPS>;
-  __shared__ __attribute__((aligned(16))) char smem[G::LDS];
+  static_assert(!TAIL || TAPS == 3, "the ConvT tail follows the decoder chain");
+  __shared__ __attribute__((aligned(16))) char smem[TAIL ? G::LDS_TAIL : G::LDS];
   const int tid = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.x * EC_ROWS;
   const EcLane<G, 1> L(tid);
@@ -382,6 +442,7 @@ __global__ __launch_bounds__(EC_NTH) void res_chain_fwd_kernel(aw_res_chain_fwd_
   const int R = P.R, NC = 2 * R;
 
   ec_init<G>(smem, tid);
+  if constexpr (TAIL) *reinterpret_cast<float*>(smem + G::TBIAS + 4 * tid) = P.tail_bias[tid];
   ec_load_image<G>(smem, P.a0, row0, nbytes, tid);
   u32x2 xr[4][4];   // the residual stream x (bf16) of this lane's fragments, kept in registers through the chain
   ec_load_frags(xr, ec_rsrc(P.x0, nbytes), ec_frag_off(row0, L.li, L.w, L.g));
@@ -405,8 +466,11 @@ __global__ __launch_bounds__(EC_NTH) void res_chain_fwd_kernel(aw_res_chain_fwd_
     const int r = c >> 1;
     const bool second = (c & 1) != 0;
     const rsrc_t rc = ec_rsrc(second ? P.w2[r] : P.w1[r], G::WBYTES);
-    const bool has_next = c + 1 < NC;
-    const rsrc_t rn = ec_rsrc(has_next ? (second ? P.w1[r + 1] : P.w2[r]) : nullptr, G::WBYTES);
+    // with a tail the weight stream runs on into its first matrix, which is packed as a 1-tap matrix
+    const bool tail_next = TAIL && c + 1 == NC;
+    const bool has_next = TAIL || c + 1 < NC;
+    const rsrc_t rn = ec_rsrc(tail_next ? P.tail_w[0] : has_next ? (second ? P.w1[r + 1] : P.w2[r]) : nullptr,
+                              tail_next ? EcGeo<1>::WBYTES : G::WBYTES);
     const int io = (c & 1) * G::IMG, no = ((c + 1) & 1) * G::IMG;
     f32x4 acc[4][4];
     // this conv's bias, one value per lane (the wave's 64 channels), loaded ahead of the K loop and parked in the
@@ -423,7 +487,12 @@ __global__ __launch_bounds__(EC_NTH) void res_chain_fwd_kernel(aw_res_chain_fwd_
       *reinterpret_cast<float*>(smem + G::BIAS + 256 * L.w + 4 * L.lane) = bias_l;
       if (DROP && second) ec_store8(rmask, (uint32_t)(ec_keep_idx(r, tid) * 8), u32x2{kb[0], kb[1]});
     };
-    ec_conv<G>(acc, wf, smem, L.rb, io, rc, rn, has_next, L.wl, L.w, c, park, hash);
+    if constexpr (TAIL)
+      ec_conv_g<G, G::KS, false>(acc, wf, smem, L.rb, io, rc, rn, true, L.wl,
+                                 tail_next ? L.w * EcGeo<1>::WWAVE + L.lane * 16 : L.wl, tail_next ? 16 : G::KS, L.w, c,
+                                 park, hash);
+    else
+      ec_conv<G>(acc, wf, smem, L.rb, io, rc, rn, has_next, L.wl, L.w, c, park, hash);
     const u32x2 keep = {kb[0], kb[1]};
     int nwb[4];   // this lane's write positions in the next image (fragment i; + JS j)
 #pragma unroll
@@ -500,8 +569,92 @@ __global__ __launch_bounds__(EC_NTH) void res_chain_fwd_kernel(aw_res_chain_fwd_
             ec_lds_w8(smem, nwb[i] + G::JS * j, xr[i][j]);
             ec_frag_fence(4 * i + j);
           }
+        if constexpr (TAIL) ec_publish<G>(smem, L.w, L.lane, c + 1);   // x_R is the tail's operand image
       }
       ec_store_slice<G, WT>(smem, no, S, ec_rsrc(P.a[r], nbytes));
+    }
+  }
+
+  if constexpr (TAIL) {
+    // The un-patch ConvT: tail_k1 independent 1-tap convs over the x_R image (image 0: NC is even), each the centre
+    // tap walk of that image with a 1-tap packed matrix.  Only the first waits for the other waves' slices.  Epilogue
+    // per fragment: v = acc + bias, column sums of v and v * v (f32, before the rounding, real rows only), bf16 into
+    // the wave's scratch and from there as whole lines into Y[row][jt H + c], 16 tokens at a time.
+    using G1 = EcGeo<1>;
+    const int k1 = P.tail_k1;
+    const int wl1 = L.w * G1::WWAVE + L.lane * 16;
+    const EcStore<G> S(tid, row0);
+    const rsrc_t ry = ec_rsrc(P.tail_y, (uint32_t)(P.N * k1 * EC_ROWB));
+    const uint32_t ygs = (uint32_t)(((row0 + (L.lane >> 3)) * k1 * EC_H + 64 * L.w + 8 * (L.lane & 7)) * 2);
+    const int st8 = 8 * k1 * EC_ROWB;
+    // 16-token groups of this row block that hold real rows (N % 16 == 0): the others are zero rows of the image,
+    // whose v = bias must enter neither Y nor the sums
+    const int64_t left = P.N - row0;
+    const int ngrp = left >= EC_ROWS ? 4 : (int)(left >> 4);
+    // [i][e]: channel 64w + 16i + 4g + e, summed over this lane's tokens and the taps -- in f64, as aw_gemm's colstats
+    // epilogue sums them (gemm_core.h): with no f32 summation order on either side the two launches' sums agree to
+    // f64 rounding, and the BatchNorm statistics made from them are the same f32 numbers
+    double cs[4][4], cq[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) cs[i][e] = cq[i][e] = 0.;
+    for (int jt = 0; jt < k1; ++jt) {
+      const bool more = jt + 1 < k1;
+      const rsrc_t rc = ec_rsrc(P.tail_w[jt], G1::WBYTES);
+      const rsrc_t rn = ec_rsrc(more ? P.tail_w[jt + 1] : nullptr, G1::WBYTES);
+      f32x4 acc[4][4];
+      ec_conv_g<G, 16, true>(acc, wf, smem, L.rb, 0, rc, rn, more, wl1, wl1, 16, L.w, jt == 0 ? NC : -1, [] {},
+                             [](int) {});
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (j < ngrp) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float4 b4 = *reinterpret_cast<const float4*>(smem + G::TBIAS + 256 * L.w + 64 * i + 16 * L.g);
+            const float bv[4] = {b4.x, b4.y, b4.z, b4.w};
+            float v[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              v[e] = acc[i][j][e] + bv[e];
+              const double vd = (double)v[e];
+              cs[i][e] += vd;
+              cq[i][e] += vd * vd;
+            }
+            ec_lds_w8(smem, S.sw[i], ec_pack(v));
+            ec_frag_fence(4 * j + i);
+          }
+          ec_store_scratch_at<G, WT>(smem, j, S, ry, ygs, st8, jt * EC_ROWB);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    // column statistics: across the 16 token lanes, then one f64 atomic pair per channel and workgroup
+    if (P.tail_colstats) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+          for (int m = 1; m < 16; m <<= 1) {
+            cs[i][e] += __shfl_xor(cs[i][e], m);
+            cq[i][e] += __shfl_xor(cq[i][e], m);
+          }
+      double* red = reinterpret_cast<double*>(smem + G::SCR + L.w * EC_SCR);   // [2][64]: the wave's channels
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the last scratch lines are read
+      if (L.li == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            red[16 * i + 4 * L.g + e] = cs[i][e];
+            red[64 + 16 * i + 4 * L.g + e] = cq[i][e];
+          }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      const double a = red[L.lane], b = red[64 + L.lane];
+      atomicAdd(P.tail_colstats + 64 * L.w + L.lane, a);
+      atomicAdd(P.tail_colstats + EC_H + 64 * L.w + L.lane, b);
     }
   }
 }
@@ -650,6 +803,7 @@ struct PackJobs {
   const void* src[AW_RES_PACK_MAX];
   void* fwd[AW_RES_PACK_MAX];
   void* bwd[AW_RES_PACK_MAX];
+  uint32_t one_tap;   // bit job: a [512][512] matrix in a launch of TAPS-tap ones (the chain tail's)
 };
 
 // blockIdx = (x, job, kind), gridDim.x = 8 TAPS.  Both kinds stage through LDS so that the global reads and writes
@@ -660,6 +814,27 @@ struct PackJobs {
 //  kind 1: tap t = x / 8, columns 64 b .. +63 (b = x % 8) of W_t (512 rows x 128 B) -> blocks (4b .. 4b + 3,
 //          16 t .. 16 t + 15) of the backward copy.
 constexpr int PK_PITCH1 = 128 + 16;       // kind 1 staging row pitch (conflict-free column reads)
+// kind 0 of a [512][512 TAPS] matrix, block rows x, x + nx, ..
+template <int TAPS>
+__device__ __forceinline__ void res_pack_fwd(const char* __restrict__ W, uint4* __restrict__ out, char* t, int x,
+                                             int nx, int tid) {
+  constexpr int RB = EC_ROWB * TAPS, PITCH0 = RB + 16, KB = 16 * TAPS;   // source row bytes, staging pitch, blocks/row
+  for (int mb = x; mb < EC_H / 16; mb += nx) {
+#pragma unroll
+    for (int q = 0; q < 4 * TAPS; ++q) {   // 16 rows x 64 TAPS chunks, row-major: coalesced
+      const int c = tid + 256 * q, row = c / (64 * TAPS), kc = c % (64 * TAPS);
+      *reinterpret_cast<uint4*>(t + row * PITCH0 + kc * 16) =
+          *reinterpret_cast<const uint4*>(W + (size_t)(16 * mb + row) * RB + kc * 16);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 4 * TAPS; ++q) {   // output chunk o = (s, lane): row lane & 15, chunk 4s + (lane >> 4)
+      const int o = tid + 256 * q, st = o >> 6, l = o & 63;
+      out[(size_t)mb * 64 * KB + o] = *reinterpret_cast<const uint4*>(t + (l & 15) * PITCH0 + (4 * st + (l >> 4)) * 16);
+    }
+    __syncthreads();
+  }
+}
 template <int TAPS>
 __global__ __launch_bounds__(256) void res_pack_kernel(PackJobs J) {
   constexpr int RB = EC_ROWB * TAPS, PITCH0 = RB + 16, KB = 16 * TAPS;   // source row bytes, kind 0 pitch, blocks/row
@@ -667,27 +842,15 @@ __global__ __launch_bounds__(256) void res_pack_kernel(PackJobs J) {
   __shared__ __attribute__((aligned(16))) char t[SZ];
   const int x = blockIdx.x, job = blockIdx.y, tid = threadIdx.x;
   const char* __restrict__ W = reinterpret_cast<const char*>(J.src[job]);
+  const bool one_tap = TAPS > 1 && ((J.one_tap >> job) & 1u);   // forward copy only (aw_res_pack_weights_mixed)
   if (blockIdx.z == 0) {
     uint4* __restrict__ out = reinterpret_cast<uint4*>(J.fwd[job]);
     if (!out) return;
-    for (int mb = x; mb < EC_H / 16; mb += gridDim.x) {
-#pragma unroll
-      for (int q = 0; q < 4 * TAPS; ++q) {   // 16 rows x 64 TAPS chunks, row-major: coalesced
-        const int c = tid + 256 * q, row = c / (64 * TAPS), kc = c % (64 * TAPS);
-        *reinterpret_cast<uint4*>(t + row * PITCH0 + kc * 16) =
-            *reinterpret_cast<const uint4*>(W + (size_t)(16 * mb + row) * RB + kc * 16);
-      }
-      __syncthreads();
-#pragma unroll
-      for (int q = 0; q < 4 * TAPS; ++q) {   // output chunk o = (s, lane): row lane & 15, chunk 4s + (lane >> 4)
-        const int o = tid + 256 * q, st = o >> 6, l = o & 63;
-        out[(size_t)mb * 64 * KB + o] = *reinterpret_cast<const uint4*>(t + (l & 15) * PITCH0 + (4 * st + (l >> 4)) * 16);
-      }
-      __syncthreads();
-    }
+    if (one_tap) res_pack_fwd<1>(W, out, t, x, (int)gridDim.x, tid);
+    else res_pack_fwd<TAPS>(W, out, t, x, (int)gridDim.x, tid);
   } else {
     uint4* __restrict__ out = reinterpret_cast<uint4*>(J.bwd[job]);
-    if (!out) return;
+    if (!out || one_tap) return;
     const int tap = x >> 3, b = x & 7;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {    // W_t[o][64 b .. +63]: 512 rows x 8 chunks
@@ -730,12 +893,12 @@ __global__ __launch_bounds__(EC_NTH) void res_mask_kernel(MaskSeeds S, const uin
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-template <int TAPS>
+template <int TAPS, bool TAIL>
 void launch_fwd(const aw_res_chain_fwd_args* a, bool drop, bool wt, dim3 grid, hipStream_t s) {
-  if (drop && wt) hipLaunchKernelGGL((res_chain_fwd_kernel<TAPS, true, true>), grid, dim3(EC_NTH), 0, s, *a);
-  else if (drop) hipLaunchKernelGGL((res_chain_fwd_kernel<TAPS, true, false>), grid, dim3(EC_NTH), 0, s, *a);
-  else if (wt) hipLaunchKernelGGL((res_chain_fwd_kernel<TAPS, false, true>), grid, dim3(EC_NTH), 0, s, *a);
-  else hipLaunchKernelGGL((res_chain_fwd_kernel<TAPS, false, false>), grid, dim3(EC_NTH), 0, s, *a);
+  if (drop && wt) hipLaunchKernelGGL((res_chain_fwd_kernel<TAPS, true, true, TAIL>), grid, dim3(EC_NTH), 0, s, *a);
+  else if (drop) hipLaunchKernelGGL((res_chain_fwd_kernel<TAPS, true, false, TAIL>), grid, dim3(EC_NTH), 0, s, *a);
+  else if (wt) hipLaunchKernelGGL((res_chain_fwd_kernel<TAPS, false, true, TAIL>), grid, dim3(EC_NTH), 0, s, *a);
+  else hipLaunchKernelGGL((res_chain_fwd_kernel<TAPS, false, false, TAIL>), grid, dim3(EC_NTH), 0, s, *a);
 }
 template <int TAPS>
 void launch_bwd(const aw_res_chain_bwd_args* a, bool drop, bool wt, dim3 grid, hipStream_t s) {
@@ -768,11 +931,23 @@ extern "C" int aw_res_chain_fwd(const aw_res_chain_fwd_args* a, void* stream) {
                "aw_res_chain_fwd: block %d saved outputs unaligned", r);
   }
   AW_REQUIRE(aligned16(a->drop_masks), "aw_res_chain_fwd: drop_masks unaligned");
+  if (a->tail_k1 == 0) {
+    AW_REQUIRE(!a->tail_bias && !a->tail_y && !a->tail_colstats, "aw_res_chain_fwd: tail fields without tail_k1");
+  } else {
+    AW_REQUIRE(a->taps == 3 && a->tail_k1 >= 1 && a->tail_k1 <= AW_RES_TAIL_MAX,
+               "aw_res_chain_fwd: the tail needs taps == 3 and tail_k1 in 1..%d (got %d)", AW_RES_TAIL_MAX, a->tail_k1);
+    AW_REQUIRE((a->N + EC_ROWS) * a->tail_k1 * EC_ROWB < (1ll << 31), "aw_res_chain_fwd: N * tail_k1 out of range");
+    AW_REQUIRE(a->tail_y && aligned16(a->tail_y) && a->tail_bias && ((uintptr_t)a->tail_colstats & 7) == 0,
+               "aw_res_chain_fwd: tail_y / tail_bias missing or unaligned");
+    for (int j = 0; j < a->tail_k1; ++j)
+      AW_REQUIRE(a->tail_w[j] && aligned16(a->tail_w[j]), "aw_res_chain_fwd: tail matrix %d missing or unaligned", j);
+  }
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)((a->N + EC_ROWS - 1) / EC_ROWS));
   const bool drop = a->drop_p > 0.f, wt = a->store_policy == AW_STORE_WT;
-  if (a->taps == 3) launch_fwd<3>(a, drop, wt, grid, s);
-  else launch_fwd<1>(a, drop, wt, grid, s);
+  if (a->tail_k1) launch_fwd<3, true>(a, drop, wt, grid, s);
+  else if (a->taps == 3) launch_fwd<3, false>(a, drop, wt, grid, s);
+  else launch_fwd<1, false>(a, drop, wt, grid, s);
   return aw::check_launch("aw_res_chain_fwd");
 }
 
@@ -800,6 +975,11 @@ extern "C" int aw_res_chain_bwd(const aw_res_chain_bwd_args* a, void* stream) {
 
 extern "C" int aw_res_pack_weights(const void* const* src, void* const* fwd, void* const* bwd, int n, int taps,
                                    void* stream) {
+  return aw_res_pack_weights_mixed(src, fwd, bwd, nullptr, n, taps, stream);
+}
+
+extern "C" int aw_res_pack_weights_mixed(const void* const* src, void* const* fwd, void* const* bwd,
+                                         const int* job_taps, int n, int taps, void* stream) {
   AW_REQUIRE(src && fwd && bwd && n >= 0 && n <= AW_RES_PACK_MAX && (taps == 1 || taps == 3),
              "aw_res_pack_weights: bad args (n must be 0..%d, taps 1 or 3)", AW_RES_PACK_MAX);
   if (n == 0) return AW_OK;
@@ -810,6 +990,11 @@ extern "C" int aw_res_pack_weights(const void* const* src, void* const* fwd, voi
     J.src[i] = src[i];
     J.fwd[i] = fwd[i];
     J.bwd[i] = bwd[i];
+    if (job_taps && job_taps[i] != taps) {
+      AW_REQUIRE(job_taps[i] == 1 && fwd[i] && !bwd[i], "aw_res_pack_weights: job %d: a job of %d taps in a launch of "
+                 "%d (only 1-tap forward copies may differ)", i, job_taps[i], taps);
+      J.one_tap |= 1u << i;
+    }
   }
   const dim3 grid(8 * taps, n, 2);
   if (taps == 3) hipLaunchKernelGGL(res_pack_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, J);
