@@ -587,6 +587,41 @@ int aw_gru_step_bwd(int B, int H, int op_dtype, const void* dgh_next_op, const f
  * bf16-rounded operand copy); one owner per column and a fixed summation order, so it is deterministic. */
 int aw_gru_bias_grad(const float* dg, int64_t rows, int H, float* db, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ generation
+ * Ids back to the decoder's input (arcweld.vqvae.decode).  In eval the decoder's 1x1 conv depends on the id alone, so
+ * aw_gemm computes y0 = E . Wd0^T + b and GELU(y0) once over the K codebook rows (table_x (K, H, x_dtype), table_a
+ * (K, H, a_dtype)) and this launch copies row idx[n] of each table to row n of y0 (N, H, x_dtype) / ya0 (N, H, a_dtype);
+ * one wave per row, 16 bytes per access (rows must be whole 16-byte pieces, every buffer 16-B aligned).
+ * Every id is range-checked in the kernel: an id outside [0, K) reads nothing, writes a zero row and adds 1 to
+ * *bad_count (a device int the caller zeroed).  table_a = ya0 = NULL gathers one table only (H = D over the codebook
+ * itself: the K > N route, where the GEMM runs over the N gathered rows instead). */
+int aw_vq_decode_gather(const int64_t* idx, int64_t N, const void* table_x, const void* table_a, int K, int H,
+                        int x_dtype, int a_dtype, void* y0, void* ya0, int* bad_count, void* stream);
+/* The next token of each of B sequences from logits (B, V) f32 (contiguous rows), one workgroup per row with the row
+ * in LDS; V <= AW_SAMPLE_MAX_V (a larger V returns AW_ERR_ARG and launches nothing).  Per row, following the
+ * reference's loop (model/transformer_decoder.py:203-224) with a column mask and a temperature added:
+ *   - only columns < n_valid take part (n_valid = V: all), x = logit * inv_temperature;
+ *   - top_k > 0: every x strictly below the top_k-th largest is dropped; ties at the threshold stay (top_k <= n_valid);
+ *   - do_sample = 0: the first index of the maximum;
+ *   - do_sample = 1: p = softmax of what is left (max-subtracted, f32); the first index whose inclusive prefix sum in
+ *     index order exceeds u * total, or the last finite kept column when rounding leaves none, with
+ *       u = draw24(seed, c = step * B + row) * 2^-24   in [0, 1),
+ *       draw24: key = aw_hash_group(seed, c >> 24); l = (c >> 12) & 0xFFF; r = c & 0xFFF;
+ *               4 times, i = 0..3: (l, r) = (r, l ^ (aw_hash_group(key + i, r) >> 52)); return l << 12 | r
+ *       aw_hash_group(s, g): z = s + (g + 1) * 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *                            z = (z ^ z >> 27) * 0x94D049BB133111EB; return z ^ z >> 31      (64-bit, wrapping)
+ *     -- a keyed permutation (4-round Feistel) of the counter's low 24 bits, its round function the counter hash of
+ *     the dropout masks: the 2^24 counters that share c >> 24 draw 2^24 different values, so one seed never repeats
+ *     a draw within a generation (the hash's plain top 24 bits would: 4096 of them collide with probability 0.39).
+ *     u_out (B f32, or NULL) receives u;
+ *   - the id goes to ids_out[row * ld_ids + col] (int64);
+ *   - a row with a NaN among its columns < n_valid, or whose maximum there is not finite, stores -1 and adds 1 to
+ *     *bad_count (a device int the caller zeroed). */
+#define AW_SAMPLE_MAX_V 16384
+int aw_sample_next(const float* logits, int B, int V, int n_valid, int top_k, float inv_temperature, int do_sample,
+                   uint64_t seed, int64_t step, int64_t* ids_out, int64_t ld_ids, int64_t col, float* u_out,
+                   int* bad_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

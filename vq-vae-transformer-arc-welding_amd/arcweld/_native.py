@@ -70,6 +70,7 @@ OPS_PER_SEG = 2     # AW_OPS_PER_SEG
 RES_CHAIN_MAX = 16  # AW_RES_CHAIN_MAX
 RES_PACK_MAX = 32   # AW_RES_PACK_MAX
 RES_TAIL_MAX = 8    # AW_RES_TAIL_MAX
+SAMPLE_MAX_V = 16384  # AW_SAMPLE_MAX_V
 _E = RES_CHAIN_MAX
 
 
@@ -185,6 +186,9 @@ SIGNATURES = {
     "aw_gru_step_fwd": [c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     "aw_gru_bias_grad": [c_p, c_i64, c_int, c_p, c_p],
     "aw_gru_step_bwd": [c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    "aw_vq_decode_gather": [c_p, c_i64, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p],
+    "aw_sample_next": [c_p, c_int, c_int, c_int, c_int, c_f, c_int, ctypes.c_uint64, c_i64, c_p, c_i64, c_i64, c_p,
+                       c_p, c_p],
 }
 
 RET_I64 = {"aw_gemm_workspace", "aw_wgrad_batch_workspace", "aw_res_dropout_masks_bytes"}

@@ -488,6 +488,51 @@ def vq_gather(E, idx, out, stream=None):
     call("aw_vq_gather", ptr(E), ptr(idx), idx.numel(), E.shape[1], ptr(out), stream_ptr(stream))
 
 
+def _chk_i32_counter(t, who):
+    if t.dtype != torch.int32 or t.numel() != 1:
+        raise nat.NativeError(f"{who}: bad_count must be one int32 on the device")
+
+
+def vq_decode_gather(idx, table_x, table_a, y0, ya0, bad_count, stream=None):
+    """aw_vq_decode_gather: y0[n] = table_x[idx[n]] (and ya0[n] = table_a[idx[n]] unless both are None), range-checked
+    in the kernel: an id outside [0, K) leaves a zero row and adds 1 to bad_count (an int32 the caller zeroed)."""
+    Kc, H = table_x.shape
+    N = idx.numel()
+    if idx.dtype != torch.int64 or not idx.is_contiguous():
+        raise nat.NativeError("vq_decode_gather: idx must be a contiguous int64 tensor")
+    if (table_a is None) != (ya0 is None):
+        raise nat.NativeError("vq_decode_gather: table_a and ya0 go together")
+    for nm, tab, out in (("x", table_x, y0), ("a", table_a, ya0)):
+        if tab is None:
+            continue
+        if (tuple(tab.shape) != (Kc, H) or tuple(out.shape) != (N, H) or out.dtype != tab.dtype
+                or not tab.is_contiguous() or not out.is_contiguous()):
+            raise nat.NativeError(f"vq_decode_gather: table_{nm} must be a contiguous ({Kc}, {H}) tensor and its output "
+                                  f"a contiguous ({N}, {H}) tensor of the same dtype")
+    _chk_i32_counter(bad_count, "vq_decode_gather")
+    call("aw_vq_decode_gather", ptr(idx), N, ptr(table_x), ptr(table_a), Kc, H, dtype_code(table_x.dtype),
+         dtype_code(table_a.dtype) if table_a is not None else AW_F32, ptr(y0), ptr(ya0), ptr(bad_count),
+         stream_ptr(stream))
+
+
+def sample_next(logits, ids_out, col, bad_count, n_valid=None, top_k=0, inv_temperature=1.0, do_sample=False, seed=0,
+                step=0, u_out=None, stream=None):
+    """aw_sample_next: the next token of each row of logits (B, V) f32 into ids_out[:, col] ((B, >= col + 1) int64);
+    see include/arcweld_amd.h for the semantics.  u_out (B,) f32 receives the uniform draws when given."""
+    B, V = logits.shape
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise nat.NativeError("sample_next: logits must be a contiguous (B, V) float32 tensor")
+    if (ids_out.dtype != torch.int64 or ids_out.dim() != 2 or ids_out.shape[0] != B or ids_out.stride(1) != 1
+            or not 0 <= col < ids_out.shape[1]):
+        raise nat.NativeError(f"sample_next: ids_out must be a (B, > {col}) int64 tensor with contiguous rows")
+    if u_out is not None and (u_out.dtype != torch.float32 or u_out.numel() != B or not u_out.is_contiguous()):
+        raise nat.NativeError("sample_next: u_out must be a contiguous (B,) float32 tensor")
+    _chk_i32_counter(bad_count, "sample_next")
+    call("aw_sample_next", ptr(logits), B, V, V if n_valid is None else int(n_valid), int(top_k or 0),
+         float(inv_temperature), int(bool(do_sample)), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), ptr(ids_out),
+         ids_out.stride(0), int(col), ptr(u_out), ptr(bad_count), stream_ptr(stream))
+
+
 # ------------------------------------------------------------------------------------------ layouts
 def patchify(x, P, out, stream=None):
     B, L, C = x.shape

@@ -30,6 +30,26 @@ def encode_ids(vqvae, x, window_size=None, dtype=torch.float32):
     return idx.view(B, -1)
 
 
+def ids_per_window(vqvae):
+    """S: the ids one window of the VQ-VAE becomes (seq_len * input_dim / patch_size)."""
+    return vqvae.seq_len * vqvae.input_dim // vqvae.patch_size
+
+
+@torch.no_grad()
+def decode_ids(vqvae, ids, dtype=None):
+    """ids (B, n_cycles*S) int64 -> x_hat (B, n_cycles*seq_len, C) f32: the inverse of ``encode_ids``'s window order
+    (window i of a sequence comes from ids [i*S, (i+1)*S)), all windows in one decoder pass
+    (arcweld.vqvae.decode).  ``dtype=None``: the process operand setting."""
+    if ids.dim() != 2:
+        raise ValueError(f"expected ids of shape (B, n_cycles*S), got {tuple(ids.shape)}")
+    S = ids_per_window(vqvae)
+    B, LT = ids.shape
+    if LT == 0 or LT % S:
+        raise ValueError(f"id sequence length {LT} is not a multiple of the {S} ids per window")
+    x = engine.decode(vqvae, ids.reshape(-1), dtype=dtype)
+    return x.view(B, (LT // S) * x.shape[1], x.shape[2])
+
+
 def autoregressive_pairs(ids, start_token=None):
     """[start, ids] -> [ids, end] (base_dataloader.py:84-97).  start = max id + 1 and end = max id + 2 over the
     whole id set (data-dependent, like the reference) unless ``start_token`` is given.

@@ -353,6 +353,78 @@ def encode(m, x, dtype=F32):
     return idx, z
 
 
+@torch.no_grad()
+@K.store_policy(nat.AW_STORE_WT)      # as forward(): the same GEMM chain
+def decode(m, idx, dtype=None):
+    """Ids back to signals: codebook indices (W*S,) int64 -> x_hat (W, L, C) f32 -- the mirror of ``encode``, the
+    second half of ``forward`` with eval semantics: no dropout, the un-patch BatchNorm on its running statistics
+    (which it leaves alone) whatever the module mode; BatchNorm ResBlocks follow the module mode, as in ``encode``.
+    ``dtype=None`` is the process operand setting (arcweld.precision).
+
+    In eval the decoder's 1x1 conv depends on the id alone, so it runs once over the K codebook rows (y0 and GELU(y0)
+    tables, one aw_gemm) and aw_vq_decode_gather copies row idx[n] of each to token n; with more codes than tokens the
+    codebook rows are gathered first and the GEMM runs over the N tokens.  Either gather checks every id in the
+    kernel: an id outside [0, K) reads nothing, and the call raises ValueError once its launches are queued."""
+    if getattr(m, "use_improved_vq", False):
+        raise NotImplementedError("decode: ids -> signals is not implemented for use_improved_vq=True (the EMA "
+                                  "residual quantizer keeps no codebook parameter to look the ids up in)")
+    T = operand_dtype(dtype)
+    if idx.dtype != torch.int64 or idx.dim() != 1:
+        raise ValueError("decode expects a flat int64 tensor of W*S codebook indices")
+    sh = VQVAEShapes(m, 1)
+    H, D, S, R, k1, Kc = sh.H, sh.D, sh.S, sh.R, sh.k1, sh.K
+    N = idx.numel()
+    if N == 0 or N % S:
+        raise ValueError(f"decode: {N} ids are not a positive multiple of the {S} ids of one window")
+    W = N // S
+    idx = idx.contiguous()
+    pr = _params(m)
+    dev = idx.device
+    e = lambda *s, dt=F32: torch.empty(*s, device=dev, dtype=dt)  # noqa: E731
+    RT = resid_dtype(m, T)
+    ops = operands.get(m, ("vqvae", T), lambda: _operand_jobs(m, T))
+    Wd0, Wt1 = ops["Wd0"], ops["Wt1"]
+    dec_w = [(ops[f"dec{r}_1"], ops[f"dec{r}_2"]) for r in range(R)]
+
+    # ---- decoder 1x1 conv: over the codebook + a two-table gather, or (K > N) a codebook gather + the GEMM
+    bad = torch.zeros(1, device=dev, dtype=torch.int32)
+    y0, ya0 = e(N, H, dt=RT), e(N, H, dt=T)
+    E = pr["E"]
+    if Kc <= N:
+        table_x, table_a = e(Kc, H, dt=RT), e(Kc, H, dt=T)
+        K.gemm(_operand(E, T), Wd0, Kc, H, D, bias=pr["dec0"].bias, C=table_x, C2=table_a, c2_mode=1)
+        K.vq_decode_gather(idx, table_x, table_a, y0, ya0, bad)
+    else:
+        zq = e(N, D)
+        K.vq_decode_gather(idx, E, None, zq, None, bad)
+        K.gemm(_operand(zq, T), Wd0, N, H, D, bias=pr["dec0"].bias, C=y0, C2=ya0, c2_mode=1)
+
+    # ---- decoder ResBlocks + un-patch ConvT, on the routes forward() takes (chain, ConvT tail)
+    bf_y = T != F32 and K.head_bf16_ok(H) and os.environ.get("ARCWELD_HEAD_BF16", "1") == "1"
+    Y = e(N, k1 * H, dt=T if bf_y else F32)
+    dec_chain = K.res_chain_ok(H, R, T, RT, 3, S, "DEC") and pr["dec_bn"] is None
+    convt_tail = dec_chain and bf_y and k1 <= nat.RES_TAIL_MAX and K.convt_tail_ok()
+    _, yR_T, _ = resstack.forward(resstack.Geometry(3, H, S), y0, ya0, dec_w, _biases(pr["dec"]), pr["dec_bn"],
+                                  T=T, RT=RT, training=m.training, chain=dec_chain, save=False,
+                                  tail=(Wt1, pr["t1"].bias, Y, None) if convt_tail else None)
+    if R == 0:
+        yR_T = _operand(y0, T)
+    if not convt_tail:
+        K.gemm(yR_T, Wt1, N, k1 * H, H, bias=pr["t1"].bias, bias_mod=H, C=Y)
+
+    # ---- head on the running statistics
+    bn = pr["bn"]
+    stats = e(4 * H)
+    K.bn_finalize(None, N * k1, H, bn.weight, bn.bias, bn.running_mean, bn.running_var, None, bn.eps,
+                  bn.momentum if bn.momentum is not None else 0.1, False, stats)
+    x_hat = e(W, sh.L, sh.C)
+    K.unpatch_head_fwd(Y.view(N * k1, H), sh.Q, stats, pr["t2"].weight.view(H, 5), pr["t2"].bias, x_hat)
+    nbad = int(bad.item())
+    if nbad:
+        raise ValueError(f"decode: {nbad} of {N} ids lie outside the codebook [0, {Kc})")
+    return x_hat
+
+
 def _cast(t, T):
     out = torch.empty(t.shape, device=t.device, dtype=T)
     K.cast(t, out)

@@ -13,6 +13,7 @@ import torch
 from torch import nn
 
 from arcweld import decoder as engine
+from arcweld import kernels as K
 from arcweld.lightning import LightningModule
 from arcweld.optim import RAdam
 from model.embedding import LatentEmbedding
@@ -289,6 +290,50 @@ class MyTransformerDecoder(LightningModule):
                 _, idx_next = torch.topk(probs, k=1, dim=-1)
             x = torch.cat([x, idx_next], dim=-1)
         return x
+
+    @torch.no_grad()
+    def generate_ids(self, x, n_new, do_sample=False, top_k=None, temperature=1.0, valid_ids=None, seed=0):
+        """ids (B, L0) -> (B, L0 + n_new) int64: n_new tokens appended by one prefill and one cached decode step per
+        token, each followed by ONE launch that picks the token (aw_sample_next: column mask, temperature, top-k
+        filter, softmax, greedy or multinomial pick) and writes it into the preallocated result -- no torch op per
+        token beyond what ``forward_cached`` does.
+
+        valid_ids: only ids < valid_ids can be produced (None: the whole vocabulary); ``valid_ids = n_classes - 2``
+        keeps the start and end tokens out, so that every generated id has a codebook row.  temperature divides the
+        logits.  do_sample draws from the counter hash of (seed, step, row): the same seed gives the same ids.
+        Needs L0 + n_new <= seq_len (the cropped-window re-prefill of ``generate`` is not carried over).  A row
+        whose logits hold a NaN or no finite value raises RuntimeError at the end."""
+        if x.dim() != 2 or x.dtype != torch.int64:
+            raise ValueError("generate_ids expects int64 ids of shape (B, L0)")
+        B, L0 = x.shape
+        n_new = int(n_new)
+        if L0 < 1 or n_new < 0 or L0 + n_new > self.seq_len:
+            raise ValueError(f"generate_ids: prompt length {L0} + n_new {n_new} must lie in 1..seq_len = {self.seq_len}")
+        V = self.n_classes
+        n_valid = V if valid_ids is None else int(valid_ids)
+        if not 1 <= n_valid <= V:
+            raise ValueError(f"generate_ids: valid_ids = {valid_ids} outside 1..n_classes = {V}")
+        k = 0 if top_k is None else int(top_k)
+        if top_k is not None and not 1 <= k <= n_valid:
+            raise ValueError(f"generate_ids: top_k = {top_k} outside 1..{n_valid} allowed ids")
+        if not (temperature > 0 and math.isfinite(temperature)):
+            raise ValueError(f"generate_ids: temperature must be positive and finite, got {temperature}")
+        out = torch.empty(B, L0 + n_new, dtype=torch.int64, device=x.device)
+        out[:, :L0] = x
+        if n_new == 0:
+            return out
+        bad = torch.zeros(1, dtype=torch.int32, device=x.device)
+        cache = engine.KVCache(self, B, self.seq_len)     # as generate(): the same decode launches, the same logits
+        for i in range(n_new):
+            pos = L0 + i                # the column this step fills
+            logits = engine.forward_cached(self, out[:, :L0], cache, 0) if i == 0 else \
+                engine.forward_cached(self, out[:, pos - 1:pos], cache, pos - 1)
+            K.sample_next(logits, out, pos, bad, n_valid=n_valid, top_k=k, inv_temperature=1.0 / temperature,
+                          do_sample=do_sample, seed=seed, step=i)
+        nbad = int(bad.item())
+        if nbad:
+            raise RuntimeError(f"generate_ids: {nbad} sampling steps met logits with a NaN or no finite value")
+        return out
 
     def loss_gen(self, logits, labels):
         return engine.cross_entropy(logits.view(-1, logits.size(-1)), labels.view(-1), ignore_index=-1)

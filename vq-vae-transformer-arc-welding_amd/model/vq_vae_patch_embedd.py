@@ -241,3 +241,14 @@ class VQVAEPatch(Autoencoder):
         fused patch_embed -> encoder -> VQ on the HIP path (eval-mode semantics of the current module state)."""
         from arcweld import tokenize
         return tokenize.encode_ids(self, x)
+
+    @torch.no_grad()
+    def decode_ids(self, ids):
+        """The way back from ``encode_ids``: ids (B, S) int64 -> windows (B, seq_len, input_dim) f32 through the
+        decoder half on the HIP path (arcweld.vqvae.decode: eval semantics, the un-patch BatchNorm on its running
+        statistics).  An id outside [0, num_embeddings) is a ValueError; use_improved_vq=True is not supported."""
+        if self.use_improved_vq:
+            raise NotImplementedError("decode_ids is not implemented for use_improved_vq=True: the EMA residual "
+                                      "quantizer's way back from ids is not built")
+        from arcweld import tokenize
+        return tokenize.decode_ids(self, ids)
