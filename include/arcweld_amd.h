@@ -622,6 +622,37 @@ int aw_sample_next(const float* logits, int B, int V, int n_valid, int top_k, fl
                    uint64_t seed, int64_t step, int64_t* ids_out, int64_t ld_ids, int64_t col, float* u_out,
                    int* bad_count, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ scoring
+ * Teacher-forced scoring of lm-head logits in one launch (MyTransformerDecoder.score_ids, arcweld.generate.score_cycles).
+ * logits: f32 rows of V columns, ldl >= V floats apart; the row of position t of sequence b is b * seq_rows + t.
+ * Sequence b has `groups` groups of `group_rows` consecutive rows, group c = rows t in [c * group_rows, (c + 1) *
+ * group_rows); groups * group_rows <= seq_rows, and the rows past them (the position that predicts the end token) and
+ * the columns >= V of a padded row are never read.  targets, logp, rank, entropy: (n_seq, groups * group_rows)
+ * compact; group_nll: (n_seq, groups).  For a row with target y, over the allowed columns j < n_valid only (the
+ * softmax renormalised over them, the restriction aw_sample_next applies), all in f32:
+ *   - logp    = l[y] - lse,  lse = mx + log sum_j exp(l[j] - mx)   (a -inf target logit in a finite row gives -inf);
+ *   - rank    = the number of j with l[j] > l[y], or l[j] == l[y] and j < y: 0 means the greedy aw_sample_next picks y;
+ *   - entropy = lse - sum_j p_j l[j], evaluated as log(sum e) - sum e (l - mx) / sum e; columns with p_j == 0 add 0;
+ *   - group_nll[b, c] = -(sum of the group's logp), summed per wave in row order and then over the waves in order
+ *     inside the workgroup that scored the rows: no floating-point atomics, the same bits on every launch.
+ * A row is bad when its allowed columns hold a NaN, a +inf or no finite value (as in aw_sample_next: no finite maximum
+ * to subtract), or when its target lies outside [0, n_valid) -- checked before it selects anything.  A bad row stores
+ * logp = NaN, rank = -1, entropy = NaN, makes its group's group_nll NaN and adds 1 to *bad_count (a device int the
+ * caller zeroed; one integer atomic per workgroup at most).
+ * One workgroup per (b, c), one wave per row; rows of n_valid <= 1024 are held in registers, wider ones are read
+ * twice.  Any V >= 1, 1 <= n_valid <= V, groups >= 1, group_rows >= 1; n_seq * groups < 2^31. */
+int aw_score_rows(const float* logits, int64_t ldl, int V, int n_valid, const int64_t* targets, int64_t n_seq,
+                  int seq_rows, int groups, int group_rows, float* logp, int* rank, float* entropy, float* group_nll,
+                  int* bad_count, void* stream);
+/* out[w] = the mean over window w's rows_per_window x width elements of (a[r, c] - b'[r, c])^2, r = w *
+ * rows_per_window ..; a: (windows * rows_per_window, width) f32 contiguous.  idx == NULL: b' = b, the same shape.
+ * idx (windows * rows_per_window int64): b'[r] = b[idx[r]], b: (n_idx_rows, width) -- the quantisation error of a
+ * cycle, encoder rows against their codebook rows.  An idx[r] outside [0, n_idx_rows) is never used as an index: it
+ * adds 1 to *bad_count (a device int the caller zeroed) and its window becomes NaN.  One workgroup per window, 16-byte
+ * loads when width is a multiple of 4 and a, b are 16-byte aligned, a fixed summation order (no float atomics). */
+int aw_window_sqerr(const float* a, const float* b, const int64_t* idx, int64_t n_idx_rows, int64_t windows,
+                    int rows_per_window, int width, float* out, int* bad_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,5 +5,6 @@ arcweld.kernels   thin typed wrappers (one per C entry point) taking torch devic
 arcweld.vqvae     autograd Functions + the fused VQ-VAE-Patch step engine
 arcweld.optim     flat-buffer RAdam / clip (multi-tensor, HIP)
 arcweld.trainer   the Lightning-equivalent fit loop (clip, accumulate, DDP over RCCL)
-arcweld.generate  weld cycles from a prompt: encode_ids -> generate_ids -> decode_ids
+arcweld.generate  weld cycles from a prompt: encode_ids -> generate_ids -> decode_ids; measured cycles scored under
+                  the two models: score_cycles (token likelihoods, reconstruction and quantisation error per cycle)
 """

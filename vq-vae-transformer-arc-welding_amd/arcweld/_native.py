@@ -189,6 +189,8 @@ SIGNATURES = {
     "aw_vq_decode_gather": [c_p, c_i64, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p],
     "aw_sample_next": [c_p, c_int, c_int, c_int, c_int, c_f, c_int, ctypes.c_uint64, c_i64, c_p, c_i64, c_i64, c_p,
                        c_p, c_p],
+    "aw_score_rows": [c_p, c_i64, c_int, c_int, c_p, c_i64, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p],
+    "aw_window_sqerr": [c_p, c_p, c_p, c_i64, c_i64, c_int, c_int, c_p, c_p, c_p],
 }
 
 RET_I64 = {"aw_gemm_workspace", "aw_wgrad_batch_workspace", "aw_res_dropout_masks_bytes"}

@@ -4,6 +4,10 @@ The three trained pieces end to end, all on the device: the frozen VQ-VAE encode
 (arcweld.tokenize.encode_ids), the Transformer continues the id sequence (MyTransformerDecoder.generate_ids: one cached
 decode step and one aw_sample_next launch per token, restricted to the codebook ids), and the VQ-VAE decoder half
 turns every id back into a window (arcweld.tokenize.decode_ids, aw_vq_decode_gather).
+
+``score_cycles`` is the mirror for cycles that were measured: the same two models, the same id layout and the same
+restriction to the codebook ids, but the ids come from the encoder and the Transformer only says how likely each one
+was (aw_score_rows), beside the VQ-VAE's own reconstruction and quantisation errors per cycle (aw_window_sqerr).
 """
 from __future__ import annotations
 
@@ -41,3 +45,59 @@ def continue_cycles(vqvae, decoder, x_prompt, n_cycles, do_sample=False, top_k=N
                                valid_ids=start, seed=seed)
     ids = out[:, 1:].contiguous()
     return {"ids": ids, "x_hat": tokenize.decode_ids(vqvae, ids, dtype=dtype)}
+
+
+@torch.no_grad()
+def score_cycles(vqvae, decoder, x, dtype=None):
+    """How well the two trained models explain measured cycles: x (B, n*L, C) f32, n >= 1 whole cycles ->
+
+      ids (B, n*S) int64      logp, entropy (B, n*S) f32      rank (B, n*S) int32
+      cycle_nll (B, n) f32    recon_mse (B, n) f32            vq_mse (B, n) f32
+
+    ids are the cycles' codebook ids (``encode_ids``).  logp / rank / entropy score every id under the Transformer
+    given the ids before it (MyTransformerDecoder.score_ids, restricted to the codebook ids as ``continue_cycles``
+    generates), cycle_nll is -logp summed over a cycle's S ids.  Cycle 0 is scored with only the start token as
+    context, so its figures say less than those of the cycles after it.  recon_mse is the mean squared error of the
+    VQ-VAE's reconstruction of each cycle (``decode_ids`` of its ids), vq_mse that between the encoder output and the
+    codebook rows it was quantised to -- for the plain VectorQuantizer what ``forward_ood``'s loss_OOD is for the
+    residual one.
+
+    The Transformer must fit the VQ-VAE as in ``continue_cycles`` (seq_len = n_cycles*S + 1, n_classes = K + 2) with
+    n <= n_cycles; scoring fewer cycles gives the first cycles' scores of the full run.  ``dtype``: the VQ-VAE's
+    operand dtype on both ways (None: exact fp32 ids, the process setting for the way back).  One encoder pass, one
+    Transformer forward, one aw_score_rows launch, one decoder pass and two aw_window_sqerr launches."""
+    if getattr(vqvae, "use_improved_vq", False):
+        raise ValueError("score_cycles: use_improved_vq=True is not supported (the EMA residual quantizer keeps no "
+                         "codebook parameter to decode the ids with or to measure the quantisation error against)")
+    S = tokenize.ids_per_window(vqvae)
+    L, Kc, D = vqvae.seq_len, vqvae.num_embeddings, vqvae.embedding_dim
+    if (decoder.seq_len - 1) % S or decoder.seq_len <= S or decoder.n_classes != Kc + 2:
+        raise ValueError(f"score_cycles: the Transformer (seq_len {decoder.seq_len}, n_classes {decoder.n_classes}) "
+                         f"does not fit this VQ-VAE: it needs seq_len = n_cycles*S + 1 with S = {S} and n_classes = "
+                         f"num_embeddings + 2 = {Kc + 2}")
+    n_model = (decoder.seq_len - 1) // S
+    if (not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 3 or x.shape[2] != vqvae.input_dim
+            or x.shape[1] % L or not L <= x.shape[1] <= n_model * L):
+        raise ValueError(f"score_cycles: x must be float32 (B, n*{L}, {vqvae.input_dim}) with 1 <= n <= n_cycles = "
+                         f"{n_model}, got {getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
+    from . import kernels as K
+    from . import vqvae as engine
+    B, n = x.shape[0], x.shape[1] // L
+    x = x.contiguous()
+    kw = {} if dtype is None else dict(dtype=dtype)          # encode's own default is exact fp32
+    idx, z = engine.encode(vqvae, x.view(B * n, L, x.shape[2]), **kw)
+    ids = idx.view(B, n * S)
+    start = decoder.n_classes - 2
+    seq = torch.cat([torch.full_like(ids[:, :1], start), ids], dim=1)
+    sc = decoder.score_groups(seq, n, S, valid_ids=start, who="score_cycles")
+    x_hat = tokenize.decode_ids(vqvae, ids, dtype=dtype)
+    recon, vq = torch.empty(B, n, device=x.device), torch.empty(B, n, device=x.device)
+    bad = torch.zeros(1, dtype=torch.int32, device=x.device)
+    K.window_sqerr(x.view(B * n, L, x.shape[2]), x_hat.view(B * n, L, x.shape[2]), recon, bad)
+    K.window_sqerr(z.view(B * n, S, D), vqvae.vector_quantization.embedding.weight.detach(), vq, bad,
+                   idx=idx.view(B * n, S))
+    nbad = int(bad.item())
+    if nbad:        # not reachable from ids the encoder made: score_groups and decode_ids have checked them already
+        raise RuntimeError(f"score_cycles: {nbad} ids lie outside the codebook [0, {Kc})")
+    return {"ids": ids, "logp": sc["logp"], "rank": sc["rank"], "entropy": sc["entropy"], "cycle_nll": sc["group_nll"],
+            "recon_mse": recon, "vq_mse": vq}

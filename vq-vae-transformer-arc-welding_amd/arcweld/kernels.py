@@ -533,6 +533,53 @@ def sample_next(logits, ids_out, col, bad_count, n_valid=None, top_k=0, inv_temp
          ids_out.stride(0), int(col), ptr(u_out), ptr(bad_count), stream_ptr(stream))
 
 
+def score_rows(logits, targets, seq_rows, groups, group_rows, logp, rank, entropy, group_nll, bad_count, n_valid=None,
+               stream=None):
+    """aw_score_rows: teacher-forced scores of logits (n_seq * seq_rows, V) f32 (rows may be padded: stride(0) >= V)
+    against targets (n_seq, groups * group_rows) int64; see include/arcweld_amd.h for the semantics.  logp, entropy
+    (f32) and rank (int32) take the targets' shape, group_nll (n_seq, groups) f32."""
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise nat.NativeError("score_rows: logits must be a (rows, V) float32 tensor with contiguous rows")
+    V = logits.shape[1]
+    seq_rows, groups, group_rows = int(seq_rows), int(groups), int(group_rows)
+    if seq_rows < 1 or groups < 1 or group_rows < 1 or groups * group_rows > seq_rows or logits.shape[0] % seq_rows:
+        raise nat.NativeError(f"score_rows: {groups} groups of {group_rows} rows do not fit sequences of {seq_rows} "
+                              f"rows, or the {logits.shape[0]} logits rows are not whole sequences")
+    n_seq = logits.shape[0] // seq_rows
+    if logits.shape[0] > 1 and logits.stride(0) < V:
+        raise nat.NativeError("score_rows: logits rows overlap (stride(0) < V)")
+    shape = (n_seq, groups * group_rows)
+    for nm, t, dt, sh in (("targets", targets, torch.int64, shape), ("logp", logp, torch.float32, shape),
+                          ("rank", rank, torch.int32, shape), ("entropy", entropy, torch.float32, shape),
+                          ("group_nll", group_nll, torch.float32, (n_seq, groups))):
+        if t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous():
+            raise nat.NativeError(f"score_rows: {nm} must be a contiguous {dt} tensor of shape {sh}, got {t.dtype} "
+                                  f"{tuple(t.shape)}")
+    _chk_i32_counter(bad_count, "score_rows")
+    call("aw_score_rows", ptr(logits), max(logits.stride(0), V), V, V if n_valid is None else int(n_valid),
+         ptr(targets), n_seq, seq_rows, groups, group_rows, ptr(logp), ptr(rank), ptr(entropy), ptr(group_nll),
+         ptr(bad_count), stream_ptr(stream))
+
+
+def window_sqerr(a, b, out, bad_count, idx=None, stream=None):
+    """aw_window_sqerr: out[w] = mean((a[w] - b'[w])^2) over a's windows a (windows, rows, width) f32.  idx None:
+    b' = b, the same shape; idx (windows, rows) int64: b'[w, r] = b[idx[w, r]] with b (n, width), each id range-checked
+    in the kernel (one outside [0, n) makes its window NaN and adds 1 to bad_count)."""
+    if a.dim() != 3 or a.dtype != torch.float32 or not a.is_contiguous():
+        raise nat.NativeError("window_sqerr: a must be a contiguous (windows, rows, width) float32 tensor")
+    W, rows, width = a.shape
+    want_b = (W, rows, width) if idx is None else (b.shape[0], width)
+    if b.dtype != torch.float32 or tuple(b.shape) != want_b or not b.is_contiguous() or b.shape[0] < 1:
+        raise nat.NativeError(f"window_sqerr: b must be a contiguous float32 tensor of shape {want_b}")
+    if idx is not None and (idx.dtype != torch.int64 or tuple(idx.shape) != (W, rows) or not idx.is_contiguous()):
+        raise nat.NativeError(f"window_sqerr: idx must be a contiguous ({W}, {rows}) int64 tensor")
+    if out.dtype != torch.float32 or out.numel() != W or not out.is_contiguous():
+        raise nat.NativeError(f"window_sqerr: out must be a contiguous float32 tensor of {W} elements")
+    _chk_i32_counter(bad_count, "window_sqerr")
+    call("aw_window_sqerr", ptr(a), ptr(b), ptr(idx), b.shape[0] if idx is not None else 0, W, rows, width, ptr(out),
+         ptr(bad_count), stream_ptr(stream))
+
+
 # ------------------------------------------------------------------------------------------ layouts
 def patchify(x, P, out, stream=None):
     B, L, C = x.shape

@@ -335,6 +335,62 @@ class MyTransformerDecoder(LightningModule):
             raise RuntimeError(f"generate_ids: {nbad} sampling steps met logits with a NaN or no finite value")
         return out
 
+    def _check_scoring(self, x, who):
+        """The argument checks of score_ids / score_groups, before any launch."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.int64:
+            raise ValueError(f"{who} expects int64 ids of shape (B, T)")
+        if not 2 <= x.shape[1] <= self.seq_len:
+            raise ValueError(f"{who}: sequence length {x.shape[1]} must lie in 2..seq_len = {self.seq_len}")
+
+    def _n_valid(self, valid_ids, who):
+        n_valid = self.n_classes if valid_ids is None else int(valid_ids)
+        if not 1 <= n_valid <= self.n_classes:
+            raise ValueError(f"{who}: valid_ids = {valid_ids} outside 1..n_classes = {self.n_classes}")
+        return n_valid
+
+    @torch.no_grad()
+    def score_groups(self, x, groups, group_rows, valid_ids=None, who="score_groups"):
+        """Teacher-forced scores of ids x (B, T) int64 with groups * group_rows == T - 1: position t predicts
+        x[:, t + 1].  One eval forward (its logits stay in the padded buffer, scored in place) and ONE aw_score_rows
+        launch; returns {"logp", "entropy" (B, T-1) f32, "rank" (B, T-1) int32, "group_nll" (B, groups) f32}, the last
+        the negative log-likelihood summed over each run of group_rows targets.  Raises RuntimeError at the end when a
+        row's logits hold a NaN or no finite value, or a target lies outside the allowed ids."""
+        self._check_scoring(x, who)
+        n_valid = self._n_valid(valid_ids, who)
+        B, T = x.shape
+        groups, group_rows = int(groups), int(group_rows)
+        if groups < 1 or group_rows < 1 or groups * group_rows != T - 1:
+            raise ValueError(f"{who}: {groups} groups of {group_rows} targets do not make the T - 1 = {T - 1} targets")
+        x = x.contiguous()
+        out, _ = engine.forward(self, x, True, False, need_backward=False)
+        logits = out.view(B * T, self.n_classes)          # rows of the padded buffer: stride(0) is its ldl
+        dev = x.device
+        targets = x[:, 1:].contiguous()
+        logp, entropy = torch.empty(B, T - 1, device=dev), torch.empty(B, T - 1, device=dev)
+        rank = torch.empty(B, T - 1, device=dev, dtype=torch.int32)
+        nll = torch.empty(B, groups, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        K.score_rows(logits, targets, T, groups, group_rows, logp, rank, entropy, nll, bad, n_valid=n_valid)
+        nbad = int(bad.item())
+        if nbad:
+            raise RuntimeError(f"{who}: {nbad} positions met logits with a NaN or no finite value, or a target "
+                               f"outside the {n_valid} allowed ids")
+        return {"logp": logp, "rank": rank, "entropy": entropy, "group_nll": nll}
+
+    @torch.no_grad()
+    def score_ids(self, x, valid_ids=None):
+        """How well the model explains measured ids: x (B, T) int64, 2 <= T <= seq_len -> {"logp", "entropy" (B, T-1)
+        f32, "rank" (B, T-1) int32} of the targets x[:, 1:] (position t predicts x[:, t + 1]).
+
+        logp is the log-probability of the target, entropy that of the predicted distribution, rank the number of
+        ids the model prefers to the target (0: greedy ``generate_ids`` would have produced it; ties break low).
+        valid_ids: the softmax is renormalised over ids < valid_ids, as ``generate_ids`` restricts its choice (None:
+        the whole vocabulary).  One eval forward and one aw_score_rows launch."""
+        self._check_scoring(x, "score_ids")
+        out = self.score_groups(x, 1, x.shape[1] - 1, valid_ids=valid_ids, who="score_ids")
+        del out["group_nll"]
+        return out
+
     def loss_gen(self, logits, labels):
         return engine.cross_entropy(logits.view(-1, logits.size(-1)), labels.view(-1), ignore_index=-1)
 
