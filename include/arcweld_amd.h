@@ -621,6 +621,48 @@ int aw_vq_decode_gather(const int64_t* idx, int64_t N, const void* table_x, cons
 int aw_sample_next(const float* logits, int B, int V, int n_valid, int top_k, float inv_temperature, int do_sample,
                    uint64_t seed, int64_t step, int64_t* ids_out, int64_t ld_ids, int64_t col, float* u_out,
                    int* bad_count, void* stream);
+/* aw_sample_next with a nucleus (top-p) and a min-p filter beside top-k, and with the likelihood of the chosen id.
+ * The same launch shape (one workgroup per row, the row in LDS, V <= AW_SAMPLE_MAX_V), the same u, and with top_p = 1
+ * and min_p = 0 the same ids bit for bit.  Per row, x_j = logit_j * inv_temperature over the columns j < n_valid,
+ * xmax their maximum, e_j = expf(x_j - xmax) in f32; the filters run in this order and each sees only the survivors
+ * of the one before:
+ *   - top_k > 0: as aw_sample_next (ties at the threshold stay);
+ *   - min_p in [0, 1), 0 = off: a column survives iff e_j >= min_p, that is p_j >= min_p * p_max whatever the
+ *     normalisation (the cut is taken at the smallest x whose e passes, so the survivors are all columns from that x up);
+ *   - top_p in (0, 1], 1 = off (no search runs): with total = the sum of e over the survivors and M(t) = the sum of e
+ *     over the survivors whose x >= t, the kept set is the survivors with x >= t*, t* the largest x of the row with
+ *     M(t*) >= top_p * total (f32 product): the smallest set of most probable columns that reaches the mass, plus every
+ *     column tied with its last member (the tie rule of top_k).  total and every M(t) are summed in one fixed order --
+ *     thread i adds its columns i, i + 256, ... in that order, a column outside the set adding +0, then a fixed tree
+ *     over the 256 threads -- so M(smallest surviving x) == total bit for bit, M is monotone in t, and t* is found by
+ *     bisection over the bits of the order-preserving 32-bit key of x below the common prefix of the smallest and the
+ *     largest surviving key: at most 32 block sums, no sort, no floating-point atomic, the same t* on every launch;
+ *   - do_sample = 0: the first index of the maximum (no filter can remove it); the filters are then evaluated only when
+ *     n_kept_out or thr_out asks for their result;
+ *   - do_sample = 1: aw_sample_next's walk in index order over the kept columns with the same u.
+ * Outputs; u_out, logp_out, logq_out, n_kept_out, thr_out may each be NULL (skipped):
+ *   - ids_out[row * ld_ids + col], u_out[row]: as aw_sample_next;
+ *   - logp_out[row * ld_lp + col_lp] = l[id] - lse,  lse = mx + log sum_j exp(l[j] - mx) over the RAW logits of the
+ *     columns j < n_valid: no temperature, no filter -- aw_score_rows' logp of that id, so generated and measured ids
+ *     sit on one scale;
+ *   - logq_out[row * ld_lp + col_lp] = log(e_id / sum of e over the kept set), the log-probability of the id under the
+ *     distribution it was drawn from; 0 when do_sample = 0;
+ *   - n_kept_out[row] (int): the number of columns < n_valid that passed all filters;
+ *   - thr_out[row]: the smallest kept x, so the kept set is exactly { j < n_valid : x_j >= thr_out[row] };
+ *   - a bad row (aw_sample_next's definition) stores id -1, logp = logq = thr = NaN, n_kept = 0 and adds 1 to *bad_count.
+ * AW_ERR_ARG and no launch for aw_sample_next's argument errors, for top_p outside (0, 1] or NaN, min_p outside [0, 1)
+ * or NaN, and for ld_lp < 1 or col_lp outside [0, ld_lp) when logp_out or logq_out is given. */
+typedef struct {
+  const float* logits; int B, V, n_valid;
+  int top_k; float top_p, min_p, inv_temperature;
+  int do_sample; uint64_t seed; int64_t step;
+  int64_t* ids_out; int64_t ld_ids, col;
+  float* u_out;
+  float* logp_out; float* logq_out; int64_t ld_lp, col_lp;
+  int* n_kept_out; float* thr_out;
+  int* bad_count;
+} aw_sample_args;
+int aw_sample_next_ex(const aw_sample_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ scoring
  * Teacher-forced scoring of lm-head logits in one launch (MyTransformerDecoder.score_ids, arcweld.generate.score_cycles).

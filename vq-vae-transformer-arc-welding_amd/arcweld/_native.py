@@ -92,6 +92,19 @@ class ResChainBwdArgs(ctypes.Structure):
                 ("gh", c_p * _E), ("gxo_out", c_p * _E),
                 ("drop_p", c_f), ("store_policy", c_int), ("drop_masks", c_p)]
 
+
+class SampleArgs(ctypes.Structure):
+    """aw_sample_args (include/arcweld_amd.h)."""
+    _fields_ = [("logits", c_p), ("B", c_int), ("V", c_int), ("n_valid", c_int),
+                ("top_k", c_int), ("top_p", c_f), ("min_p", c_f), ("inv_temperature", c_f),
+                ("do_sample", c_int), ("seed", ctypes.c_uint64), ("step", c_i64),
+                ("ids_out", c_p), ("ld_ids", c_i64), ("col", c_i64),
+                ("u_out", c_p),
+                ("logp_out", c_p), ("logq_out", c_p), ("ld_lp", c_i64), ("col_lp", c_i64),
+                ("n_kept_out", c_p), ("thr_out", c_p),
+                ("bad_count", c_p)]
+
+
 # name -> argtypes (every entry returns int status except aw_last_error)
 SIGNATURES = {
     "aw_version": [],
@@ -189,6 +202,7 @@ SIGNATURES = {
     "aw_vq_decode_gather": [c_p, c_i64, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p],
     "aw_sample_next": [c_p, c_int, c_int, c_int, c_int, c_f, c_int, ctypes.c_uint64, c_i64, c_p, c_i64, c_i64, c_p,
                        c_p, c_p],
+    "aw_sample_next_ex": [ctypes.POINTER(SampleArgs), c_p],
     "aw_score_rows": [c_p, c_i64, c_int, c_int, c_p, c_i64, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p],
     "aw_window_sqerr": [c_p, c_p, c_p, c_i64, c_i64, c_int, c_int, c_p, c_p, c_p],
 }

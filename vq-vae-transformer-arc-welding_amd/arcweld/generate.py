@@ -2,7 +2,7 @@
 
 The three trained pieces end to end, all on the device: the frozen VQ-VAE encoder turns the prompt cycles into ids
 (arcweld.tokenize.encode_ids), the Transformer continues the id sequence (MyTransformerDecoder.generate_ids: one cached
-decode step and one aw_sample_next launch per token, restricted to the codebook ids), and the VQ-VAE decoder half
+decode step and one aw_sample_next / aw_sample_next_ex launch per token, restricted to the codebook ids), and the VQ-VAE decoder half
 turns every id back into a window (arcweld.tokenize.decode_ids, aw_vq_decode_gather).
 
 ``score_cycles`` is the mirror for cycles that were measured: the same two models, the same id layout and the same
@@ -18,14 +18,20 @@ from . import tokenize
 
 @torch.no_grad()
 def continue_cycles(vqvae, decoder, x_prompt, n_cycles, do_sample=False, top_k=None, temperature=1.0, seed=0,
-                    dtype=None):
+                    dtype=None, top_p=None, min_p=None, return_logp=False):
     """x_prompt (B, c*L, C) f32, 1 <= c < n_cycles measured cycles -> {"ids": (B, n_cycles*S) int64, "x_hat":
     (B, n_cycles*L, C) f32}: the prompt's ids followed by (n_cycles - c)*S generated ones, and all of them decoded
     (the first c*L rows of x_hat are the VQ-VAE's reconstruction of the prompt).
 
     The Transformer must have been trained on [start, ids of n_cycles cycles] (tokenize.autoregressive_pairs):
     seq_len = n_cycles*S + 1 and n_classes = K + 2 with start = K, end = K + 1; generation is restricted to ids < K.
-    ``dtype``: the VQ-VAE's operand dtype on both ways (None: the process setting, arcweld.precision)."""
+    ``dtype``: the VQ-VAE's operand dtype on both ways (None: the process setting, arcweld.precision).
+
+    top_p / min_p: the nucleus and min-p cuts of ``generate_ids``.  return_logp adds, for the generated ids only,
+    "gen_logp" and "gen_logq" (B, (n_cycles - c)*S) f32 and "gen_cycle_nll" (B, n_cycles - c) f32 = -gen_logp summed
+    per cycle: gen_logp / gen_cycle_nll are on the scale of ``score_cycles``' logp / cycle_nll (the model's own
+    distribution over the codebook ids), gen_logq is the log-probability under the filtered, tempered distribution the
+    id was drawn from.  They come out of the launches that picked the ids: no second forward."""
     S = tokenize.ids_per_window(vqvae)
     L, Kc = vqvae.seq_len, vqvae.num_embeddings
     n_cycles = int(n_cycles)
@@ -42,9 +48,16 @@ def continue_cycles(vqvae, decoder, x_prompt, n_cycles, do_sample=False, top_k=N
     prompt_ids = tokenize.encode_ids(vqvae, x_prompt, **kw)
     x = torch.cat([torch.full_like(prompt_ids[:, :1], start), prompt_ids], dim=1)
     out = decoder.generate_ids(x, (n_cycles - c) * S, do_sample=do_sample, top_k=top_k, temperature=temperature,
-                               valid_ids=start, seed=seed)
+                               valid_ids=start, seed=seed, top_p=top_p, min_p=min_p, return_logp=return_logp)
+    lp = None
+    if return_logp:
+        out, lp = out
     ids = out[:, 1:].contiguous()
-    return {"ids": ids, "x_hat": tokenize.decode_ids(vqvae, ids, dtype=dtype)}
+    res = {"ids": ids, "x_hat": tokenize.decode_ids(vqvae, ids, dtype=dtype)}
+    if lp is not None:
+        res.update(gen_logp=lp["logp"], gen_logq=lp["logq"],
+                   gen_cycle_nll=-lp["logp"].view(ids.shape[0], n_cycles - c, S).sum(-1))
+    return res
 
 
 @torch.no_grad()

@@ -533,6 +533,43 @@ def sample_next(logits, ids_out, col, bad_count, n_valid=None, top_k=0, inv_temp
          ids_out.stride(0), int(col), ptr(u_out), ptr(bad_count), stream_ptr(stream))
 
 
+def sample_next_ex(logits, ids_out, col, bad_count, n_valid=None, top_k=0, top_p=1.0, min_p=0.0, inv_temperature=1.0,
+                   do_sample=False, seed=0, step=0, u_out=None, logp_out=None, logq_out=None, col_lp=0,
+                   n_kept_out=None, thr_out=None, stream=None):
+    """aw_sample_next_ex: sample_next with a min-p and a nucleus (top-p) filter after top-k, and the likelihood of the
+    chosen id; see include/arcweld_amd.h for the semantics.  logp_out / logq_out: (B, > col_lp) f32 with contiguous
+    rows (the same shape and strides when both are given), written at [:, col_lp]; n_kept_out (B,) int32 and thr_out
+    (B,) f32 receive the size of the kept set and its smallest scaled logit."""
+    B, V = logits.shape
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise nat.NativeError("sample_next_ex: logits must be a contiguous (B, V) float32 tensor")
+    if (ids_out.dtype != torch.int64 or ids_out.dim() != 2 or ids_out.shape[0] != B or ids_out.stride(1) != 1
+            or not 0 <= col < ids_out.shape[1]):
+        raise nat.NativeError(f"sample_next_ex: ids_out must be a (B, > {col}) int64 tensor with contiguous rows")
+    for nm, t, dt in (("u_out", u_out, torch.float32), ("n_kept_out", n_kept_out, torch.int32),
+                      ("thr_out", thr_out, torch.float32)):
+        if t is not None and (t.dtype != dt or t.numel() != B or not t.is_contiguous()):
+            raise nat.NativeError(f"sample_next_ex: {nm} must be a contiguous (B,) {dt} tensor")
+    lp = [t for t in (logp_out, logq_out) if t is not None]
+    for t in lp:
+        if (t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != B or t.stride(1) != 1
+                or not 0 <= col_lp < t.shape[1] or (B > 1 and t.stride(0) < t.shape[1])):
+            raise nat.NativeError(f"sample_next_ex: logp_out / logq_out must be (B, > {col_lp}) float32 tensors with "
+                                  "contiguous rows")
+    if len(lp) == 2 and (lp[0].shape != lp[1].shape or lp[0].stride() != lp[1].stride()):
+        raise nat.NativeError("sample_next_ex: logp_out and logq_out must share shape and strides (one ld_lp)")
+    _chk_i32_counter(bad_count, "sample_next_ex")
+    a = nat.SampleArgs()
+    a.logits, a.B, a.V, a.n_valid = ptr(logits), B, V, V if n_valid is None else int(n_valid)
+    a.top_k, a.top_p, a.min_p, a.inv_temperature = int(top_k or 0), float(top_p), float(min_p), float(inv_temperature)
+    a.do_sample, a.seed, a.step = int(bool(do_sample)), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step)
+    a.ids_out, a.ld_ids, a.col = ptr(ids_out), ids_out.stride(0), int(col)
+    a.u_out, a.logp_out, a.logq_out = ptr(u_out), ptr(logp_out), ptr(logq_out)
+    a.ld_lp, a.col_lp = (max(lp[0].stride(0), lp[0].shape[1]) if lp else 0), int(col_lp)
+    a.n_kept_out, a.thr_out, a.bad_count = ptr(n_kept_out), ptr(thr_out), ptr(bad_count)
+    call("aw_sample_next_ex", ctypes.byref(a), stream_ptr(stream))
+
+
 def score_rows(logits, targets, seq_rows, groups, group_rows, logp, rank, entropy, group_nll, bad_count, n_valid=None,
                stream=None):
     """aw_score_rows: teacher-forced scores of logits (n_seq * seq_rows, V) f32 (rows may be padded: stride(0) >= V)

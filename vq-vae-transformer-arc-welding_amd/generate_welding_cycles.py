@@ -10,7 +10,9 @@ cycles are generated on the device (arcweld.generate.continue_cycles) and ``--ou
   prompt (n, prompt_cycles*200, 2) f32    ids (n, n_cycles*S) int64    x_hat (n, n_cycles*200, 2) f32
 
 where x_hat[:, :prompt_cycles*200] is the VQ-VAE's reconstruction of the prompt.  ``--do-sample`` draws from the
-(``--top-k`` filtered, ``--temperature`` scaled) distribution with ``--seed``; the default is greedy.
+(``--top-k`` / ``--min-p`` / ``--top-p`` filtered, ``--temperature`` scaled) distribution with ``--seed``; the default
+is greedy.  ``--logp`` adds gen_logp, gen_logq (n, (n_cycles - prompt_cycles)*S) and gen_cycle_nll (n, n_cycles -
+prompt_cycles): the generated ids' log-probabilities on the scale of score_welding_cycles.py (continue_cycles).
 """
 import argparse
 import logging as log
@@ -34,8 +36,12 @@ def parser():
     p.add_argument('--data-npz', type=str, default="", help="real windows: its 'test' split provides the prompts")
     p.add_argument('--do-sample', action=argparse.BooleanOptionalAction, default=False)
     p.add_argument('--top-k', type=int, default=None)
+    p.add_argument('--top-p', type=float, default=None, help="nucleus: keep the fewest ids reaching this mass")
+    p.add_argument('--min-p', type=float, default=None, help="keep ids with >= this share of the mode's probability")
     p.add_argument('--temperature', type=float, default=1.0)
     p.add_argument('--seed', type=int, default=0)
+    p.add_argument('--logp', action=argparse.BooleanOptionalAction, default=False,
+                   help="also store the generated ids' log-probabilities")
     p.add_argument('--precision', choices=["fp32", "bf16"], default="fp32",
                    help="MFMA operand dtype (bf16: opt-in, fp32 accumulation)")
     p.add_argument('--out', type=str, default="generated_cycles.npz")
@@ -76,9 +82,11 @@ def main(hparams):
     decoder = MyTransformerDecoder.load_from_checkpoint(hparams.transformer_model).to(dev).eval()
     prompt = load_prompts(hparams, vqvae.seq_len, dev)
     out = continue_cycles(vqvae, decoder, prompt, hparams.n_cycles, do_sample=bool(hparams.do_sample),
-                          top_k=hparams.top_k, temperature=hparams.temperature, seed=hparams.seed)
+                          top_k=hparams.top_k, temperature=hparams.temperature, seed=hparams.seed,
+                          top_p=hparams.top_p, min_p=hparams.min_p, return_logp=bool(hparams.logp))
+    extra = {k: out[k].cpu().numpy() for k in ("gen_logp", "gen_logq", "gen_cycle_nll") if k in out}
     np.savez(hparams.out, prompt=prompt.cpu().numpy(), ids=out["ids"].cpu().numpy(),
-             x_hat=out["x_hat"].cpu().numpy())
+             x_hat=out["x_hat"].cpu().numpy(), **extra)
     log.info(f"wrote {hparams.out}: {tuple(out['ids'].shape)} ids, {tuple(out['x_hat'].shape)} signals")
     return out
 

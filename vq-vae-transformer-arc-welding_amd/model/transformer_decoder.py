@@ -292,7 +292,8 @@ class MyTransformerDecoder(LightningModule):
         return x
 
     @torch.no_grad()
-    def generate_ids(self, x, n_new, do_sample=False, top_k=None, temperature=1.0, valid_ids=None, seed=0):
+    def generate_ids(self, x, n_new, do_sample=False, top_k=None, temperature=1.0, valid_ids=None, seed=0, top_p=None,
+                     min_p=None, return_logp=False):
         """ids (B, L0) -> (B, L0 + n_new) int64: n_new tokens appended by one prefill and one cached decode step per
         token, each followed by ONE launch that picks the token (aw_sample_next: column mask, temperature, top-k
         filter, softmax, greedy or multinomial pick) and writes it into the preallocated result -- no torch op per
@@ -302,7 +303,15 @@ class MyTransformerDecoder(LightningModule):
         keeps the start and end tokens out, so that every generated id has a codebook row.  temperature divides the
         logits.  do_sample draws from the counter hash of (seed, step, row): the same seed gives the same ids.
         Needs L0 + n_new <= seq_len (the cropped-window re-prefill of ``generate`` is not carried over).  A row
-        whose logits hold a NaN or no finite value raises RuntimeError at the end."""
+        whose logits hold a NaN or no finite value raises RuntimeError at the end.
+
+        top_p in (0, 1] (nucleus: the fewest most probable ids whose mass reaches top_p) and min_p in [0, 1) (ids with
+        at least min_p times the probability of the most likely one) cut the sampled distribution after top_k, in the
+        order top_k, min_p, top_p; None is off.  return_logp: returns (ids, {"logp", "logq"}), both (B, n_new) f32:
+        logp is each generated id's log-probability under the model over the allowed ids -- no temperature, no
+        filter: what ``score_ids(ids, valid_ids)`` gives for it --, logq its log-probability under the distribution it
+        was drawn from (0 for greedy).  Any of the three switches the token launch to aw_sample_next_ex, which writes
+        straight into those two buffers; without them the call is aw_sample_next's as before."""
         if x.dim() != 2 or x.dtype != torch.int64:
             raise ValueError("generate_ids expects int64 ids of shape (B, L0)")
         B, L0 = x.shape
@@ -318,22 +327,34 @@ class MyTransformerDecoder(LightningModule):
             raise ValueError(f"generate_ids: top_k = {top_k} outside 1..{n_valid} allowed ids")
         if not (temperature > 0 and math.isfinite(temperature)):
             raise ValueError(f"generate_ids: temperature must be positive and finite, got {temperature}")
+        if top_p is not None and not 0.0 < top_p <= 1.0:
+            raise ValueError(f"generate_ids: top_p must lie in (0, 1], got {top_p}")
+        if min_p is not None and not 0.0 <= min_p < 1.0:
+            raise ValueError(f"generate_ids: min_p must lie in [0, 1), got {min_p}")
+        ex = top_p is not None or min_p is not None or return_logp
         out = torch.empty(B, L0 + n_new, dtype=torch.int64, device=x.device)
         out[:, :L0] = x
+        lp = {k: torch.empty(B, n_new, device=x.device) for k in ("logp", "logq")} if return_logp else None
         if n_new == 0:
-            return out
+            return (out, lp) if return_logp else out
         bad = torch.zeros(1, dtype=torch.int32, device=x.device)
         cache = engine.KVCache(self, B, self.seq_len)     # as generate(): the same decode launches, the same logits
         for i in range(n_new):
             pos = L0 + i                # the column this step fills
             logits = engine.forward_cached(self, out[:, :L0], cache, 0) if i == 0 else \
                 engine.forward_cached(self, out[:, pos - 1:pos], cache, pos - 1)
-            K.sample_next(logits, out, pos, bad, n_valid=n_valid, top_k=k, inv_temperature=1.0 / temperature,
-                          do_sample=do_sample, seed=seed, step=i)
+            if ex:
+                K.sample_next_ex(logits, out, pos, bad, n_valid=n_valid, top_k=k,
+                                 top_p=1.0 if top_p is None else top_p, min_p=0.0 if min_p is None else min_p,
+                                 inv_temperature=1.0 / temperature, do_sample=do_sample, seed=seed, step=i,
+                                 logp_out=lp and lp["logp"], logq_out=lp and lp["logq"], col_lp=i)
+            else:
+                K.sample_next(logits, out, pos, bad, n_valid=n_valid, top_k=k, inv_temperature=1.0 / temperature,
+                              do_sample=do_sample, seed=seed, step=i)
         nbad = int(bad.item())
         if nbad:
             raise RuntimeError(f"generate_ids: {nbad} sampling steps met logits with a NaN or no finite value")
-        return out
+        return (out, lp) if return_logp else out
 
     def _check_scoring(self, x, who):
         """The argument checks of score_ids / score_groups, before any launch."""
