@@ -664,6 +664,60 @@ typedef struct {
 } aw_sample_args;
 int aw_sample_next_ex(const aw_sample_args* args, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ beam search
+ * One step of a fixed-length beam search (MyTransformerDecoder.beam_search_ids): B sequences, each with W_in live beams,
+ * keep the W_out best of their W_in * n_valid one-token extensions.  One workgroup per sequence, the sequence's whole
+ * candidate set in LDS as the order-preserving keys of aw_sample_next.
+ *   logits: f32, B * W_in rows of V columns, ldl >= V floats apart; beam w of sequence b is row b * W_in + w.  Only the
+ *   columns v < n_valid are candidates (aw_sample_next's restriction).  scores_in: (B, W_in) f32, the beams' running
+ *   log-probabilities.  For every candidate (w, v), in f32:
+ *     logp = l[w][v] - lse_w,  lse_w = mx_w + logf(sum_{j < n_valid} expf(l[w][j] - mx_w))     (the RAW logits: the
+ *            logp of aw_score_rows and of aw_sample_next_ex), the sum in one fixed order;
+ *     cand = scores_in[b][w] + logp.
+ *   The kept set is the W_out best candidates under ONE total order -- cand descending, ties by the lower flat index
+ *   w * n_valid + v -- and slot j of the outputs is the j-th of them:
+ *     scores_out[b][j] = cand    parent_out[b][j] = w (int32, in [0, W_in))    token_out[b * W_out + j] = v (int64: the
+ *     next step's ids_new as it stands)    logp_out[b][j] = the candidate's own logp.
+ *   There is no special case for a dead beam: a score of -inf gives -inf candidates, which sort behind every finite one
+ *   and fill the tail by the same tie rule (so does a -inf logit).  When W_out exceeds the W_in * n_valid candidates
+ *   that exist, the slots past them hold score = logp = -inf, parent 0, token 0: dead beams for the next step.
+ *   The same inputs give the same bits on every launch (no floating-point atomic, fixed summation order).
+ * A sequence is bad when the allowed columns of any of its rows hold a NaN or have no finite maximum (aw_sample_next's
+ * definition), or when one of its input scores is NaN: all its slots store score = logp = NaN, parent min(j, W_in - 1),
+ * token 0, and 1 is added to *bad_count (a device int the caller zeroed).  No id outside [0, n_valid) and no parent
+ * outside [0, W_in) is ever stored: the next decode step and aw_beam_gather index with them.
+ * AW_ERR_ARG and no launch unless 1 <= W_in <= AW_BEAM_MAX_W, 1 <= W_out <= AW_BEAM_MAX_W, 1 <= n_valid <= V <= ldl and
+ * W_in * n_valid <= AW_SAMPLE_MAX_V (the largest LDS image: 32 beams at a 512-code codebook). */
+#define AW_BEAM_MAX_W 32
+typedef struct {
+  const float* logits; int64_t ldl; int B, W_in, W_out, V, n_valid;
+  const float* scores_in;
+  float* scores_out; int* parent_out; int64_t* token_out; float* logp_out;
+  int* bad_count;
+} aw_beam_args;
+int aw_beam_step(const aw_beam_args* args, void* stream);
+/* The key/value caches of all decoder blocks reordered by the surviving beams' parents, in one launch: for every block
+ * k < n_blocks, destination row r = b * W_out + j (b < B, j < W_out) and position t < n_pos
+ *     dst[k][r, t, :] = src[k][b * W_in + parent[b * W_out + j], t, :]
+ * A cache is (rows, Tmax, width) in `dtype` (AW_F32 / AW_BF16), rows [K | V] of width = 2 * d_model: the layout
+ * aw_attn_decode defines, so a row's n_pos * width elements are one contiguous chunk.  Positions >= n_pos of dst are
+ * not written.  src / dst: DEVICE arrays of n_blocks pointers (built once per search); src[k] and dst[k] are different
+ * buffers.  W_in = 1 spreads a prefill cache of B rows over B * W_out rows.  16-byte accesses when a block's two bases,
+ * the row pitch and the chunk are all multiples of 16 bytes (decided per block in the kernel), element copies
+ * otherwise: any width >= 1.  A parent outside [0, W_in) is never used as an index: its destination chunk is
+ * zero-filled and 1 is added to *bad_count (a device int the caller zeroed), once per such parent.
+ * AW_ERR_ARG unless 1 <= n_blocks <= 65535, B >= 0, 1 <= W_in, W_out <= AW_BEAM_MAX_W, 0 <= n_pos <= Tmax, width >= 1. */
+int aw_beam_gather(const void* const* src, void* const* dst, int n_blocks, int B, int W_in, int W_out,
+                   const int* parent, int Tmax, int n_pos, int width, int dtype, int* bad_count, void* stream);
+/* The hypotheses of a finished search from its per-step slabs parent (int32), token (int64), logp (f32), each
+ * (n_new, B, W) as aw_beam_step wrote them: for b < B, j < R <= W, walking back from final beam j (cur = j; for i =
+ * n_new - 1 .. 0: at = (i * B + b) * W + cur, emit, cur = parent[at]):
+ *     ids_out[(b * R + j) * ld_ids + col0 + i] = token[at]      logp_out[(b * R + j) * n_new + i] = logp[at]
+ * One thread per hypothesis.  A parent outside [0, W) met on the way ends that walk: the steps before it store id 0 and
+ * logp NaN, and 1 is added to *bad_count.  n_new >= 0, ld_ids >= col0 + n_new, col0 >= 0. */
+int aw_beam_backtrack(const int* parent, const int64_t* token, const float* logp, int n_new, int B, int W, int R,
+                      int64_t* ids_out, int64_t ld_ids, int64_t col0, float* logp_out, int* bad_count, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ scoring
  * Teacher-forced scoring of lm-head logits in one launch (MyTransformerDecoder.score_ids, arcweld.generate.score_cycles).
  * logits: f32 rows of V columns, ldl >= V floats apart; the row of position t of sequence b is b * seq_rows + t.

@@ -105,6 +105,18 @@ class SampleArgs(ctypes.Structure):
                 ("bad_count", c_p)]
 
 
+BEAM_MAX_W = 32       # AW_BEAM_MAX_W
+
+
+class BeamArgs(ctypes.Structure):
+    """aw_beam_args (include/arcweld_amd.h)."""
+    _fields_ = [("logits", c_p), ("ldl", c_i64), ("B", c_int), ("W_in", c_int), ("W_out", c_int), ("V", c_int),
+                ("n_valid", c_int),
+                ("scores_in", c_p),
+                ("scores_out", c_p), ("parent_out", c_p), ("token_out", c_p), ("logp_out", c_p),
+                ("bad_count", c_p)]
+
+
 # name -> argtypes (every entry returns int status except aw_last_error)
 SIGNATURES = {
     "aw_version": [],
@@ -203,6 +215,9 @@ SIGNATURES = {
     "aw_sample_next": [c_p, c_int, c_int, c_int, c_int, c_f, c_int, ctypes.c_uint64, c_i64, c_p, c_i64, c_i64, c_p,
                        c_p, c_p],
     "aw_sample_next_ex": [ctypes.POINTER(SampleArgs), c_p],
+    "aw_beam_step": [ctypes.POINTER(BeamArgs), c_p],
+    "aw_beam_gather": [c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_int, c_int, c_int, c_int, c_p, c_p],
+    "aw_beam_backtrack": [c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_i64, c_i64, c_p, c_p, c_p],
     "aw_score_rows": [c_p, c_i64, c_int, c_int, c_p, c_i64, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p],
     "aw_window_sqerr": [c_p, c_p, c_p, c_i64, c_i64, c_int, c_int, c_p, c_p, c_p],
 }

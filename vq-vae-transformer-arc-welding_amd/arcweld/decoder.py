@@ -386,14 +386,18 @@ def cross_entropy(logits2d, target, ignore_index=-100):
 
 class KVCache:
     """Per-block key/value cache for incremental decoding: (B, Tmax, 2d) rows [K | V] in the operand dtype, plus
-    the operand copies of the block weights (cast once per generate call)."""
+    the operand copies of the block weights (cast once per generate call).  ``share``: another KVCache of the same
+    model whose operand copies this one uses instead of casting its own (the cache sets of a beam search)."""
 
-    def __init__(self, m, B, Tmax, dtype=None):
-        self.T_ = operand_dtype(dtype)
+    def __init__(self, m, B, Tmax, dtype=None, share=None):
+        self.T_ = operand_dtype(dtype) if share is None else share.T_
         dev = m.lm_head.weight.device
         d = m.d_model
         self.B, self.Tmax = B, Tmax
         self.kv = [torch.empty(B, Tmax, 2 * d, device=dev, dtype=self.T_) for _ in m.transformer.h]
+        if share is not None:
+            self.wops, self.Wlm = share.wops, share.Wlm
+            return
         self.wops, casts = [], []
         for blk in m.transformer.h:
             ws = []

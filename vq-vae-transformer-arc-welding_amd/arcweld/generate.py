@@ -3,7 +3,9 @@
 The three trained pieces end to end, all on the device: the frozen VQ-VAE encoder turns the prompt cycles into ids
 (arcweld.tokenize.encode_ids), the Transformer continues the id sequence (MyTransformerDecoder.generate_ids: one cached
 decode step and one aw_sample_next / aw_sample_next_ex launch per token, restricted to the codebook ids), and the VQ-VAE decoder half
-turns every id back into a window (arcweld.tokenize.decode_ids, aw_vq_decode_gather).
+turns every id back into a window (arcweld.tokenize.decode_ids, aw_vq_decode_gather).  With ``num_beams`` the
+continuation is searched for instead (MyTransformerDecoder.beam_search_ids: aw_beam_step and aw_beam_gather per token)
+and the ranked hypotheses come back beside the best one.
 
 ``score_cycles`` is the mirror for cycles that were measured: the same two models, the same id layout and the same
 restriction to the codebook ids, but the ids come from the encoder and the Transformer only says how likely each one
@@ -18,7 +20,7 @@ from . import tokenize
 
 @torch.no_grad()
 def continue_cycles(vqvae, decoder, x_prompt, n_cycles, do_sample=False, top_k=None, temperature=1.0, seed=0,
-                    dtype=None, top_p=None, min_p=None, return_logp=False):
+                    dtype=None, top_p=None, min_p=None, return_logp=False, num_beams=None, num_return=1):
     """x_prompt (B, c*L, C) f32, 1 <= c < n_cycles measured cycles -> {"ids": (B, n_cycles*S) int64, "x_hat":
     (B, n_cycles*L, C) f32}: the prompt's ids followed by (n_cycles - c)*S generated ones, and all of them decoded
     (the first c*L rows of x_hat are the VQ-VAE's reconstruction of the prompt).
@@ -31,7 +33,19 @@ def continue_cycles(vqvae, decoder, x_prompt, n_cycles, do_sample=False, top_k=N
     "gen_logp" and "gen_logq" (B, (n_cycles - c)*S) f32 and "gen_cycle_nll" (B, n_cycles - c) f32 = -gen_logp summed
     per cycle: gen_logp / gen_cycle_nll are on the scale of ``score_cycles``' logp / cycle_nll (the model's own
     distribution over the codebook ids), gen_logq is the log-probability under the filtered, tempered distribution the
-    id was drawn from.  They come out of the launches that picked the ids: no second forward."""
+    id was drawn from.  They come out of the launches that picked the ids: no second forward.
+
+    num_beams (1..32): the continuation is searched for instead of drawn (MyTransformerDecoder.beam_search_ids: the
+    most probable continuations a beam of that width finds).  "ids" and "x_hat" are then the best hypothesis, and the
+    R = num_return (1..num_beams) best ones, best first, are added as "beam_ids" (B, R, n_cycles*S) int64, "beam_scores"
+    (B, R) f32 -- the log-probability of each hypothesis' generated ids, on the scale of -cycle_nll summed -- and
+    "beam_x_hat" (B, R, n_cycles*L, C) f32, all decoded in one ``decode_ids`` pass.  return_logp then gives gen_logp and
+    gen_cycle_nll of the best hypothesis and gen_logq = 0, as for greedy.  The search is deterministic: combining it with
+    do_sample, top_k, top_p, min_p or a temperature other than 1 raises ValueError."""
+    if num_beams is not None and (do_sample or top_k is not None or top_p is not None or min_p is not None
+                                  or temperature != 1):
+        raise ValueError("continue_cycles: num_beams searches the model's own distribution: it cannot be combined "
+                         "with do_sample, top_k, top_p, min_p or temperature != 1")
     S = tokenize.ids_per_window(vqvae)
     L, Kc = vqvae.seq_len, vqvae.num_embeddings
     n_cycles = int(n_cycles)
@@ -47,6 +61,18 @@ def continue_cycles(vqvae, decoder, x_prompt, n_cycles, do_sample=False, top_k=N
     kw = {} if dtype is None else dict(dtype=dtype)          # encode_ids' own default is exact fp32
     prompt_ids = tokenize.encode_ids(vqvae, x_prompt, **kw)
     x = torch.cat([torch.full_like(prompt_ids[:, :1], start), prompt_ids], dim=1)
+    if num_beams is not None:
+        bs = decoder.beam_search_ids(x, (n_cycles - c) * S, num_beams, valid_ids=start, num_return=num_return)
+        B, R = bs["scores"].shape
+        beam_ids = bs["ids"][:, :, 1:].contiguous()
+        x_hat = tokenize.decode_ids(vqvae, beam_ids.view(B * R, n_cycles * S), dtype=dtype)
+        x_hat = x_hat.view(B, R, *x_hat.shape[1:])
+        res = {"ids": beam_ids[:, 0].contiguous(), "x_hat": x_hat[:, 0].contiguous(), "beam_ids": beam_ids,
+               "beam_scores": bs["scores"], "beam_x_hat": x_hat}
+        if return_logp:
+            lp = bs["logp"][:, 0].contiguous()
+            res.update(gen_logp=lp, gen_logq=torch.zeros_like(lp), gen_cycle_nll=-lp.view(B, n_cycles - c, S).sum(-1))
+        return res
     out = decoder.generate_ids(x, (n_cycles - c) * S, do_sample=do_sample, top_k=top_k, temperature=temperature,
                                valid_ids=start, seed=seed, top_p=top_p, min_p=min_p, return_logp=return_logp)
     lp = None

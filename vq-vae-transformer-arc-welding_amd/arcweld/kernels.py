@@ -570,6 +570,87 @@ def sample_next_ex(logits, ids_out, col, bad_count, n_valid=None, top_k=0, top_p
     call("aw_sample_next_ex", ctypes.byref(a), stream_ptr(stream))
 
 
+def beam_step(logits, scores_in, scores_out, parent_out, token_out, logp_out, bad_count, n_valid=None, stream=None):
+    """aw_beam_step: the W_out best one-token extensions of each sequence's W_in beams; see include/arcweld_amd.h for
+    the semantics.  logits (B * W_in, V) f32 with contiguous rows (stride(0) is ldl), scores_in (B, W_in) f32; the
+    outputs are contiguous with B * W_out elements each -- scores_out, logp_out f32, parent_out int32, token_out int64
+    -- typically one step's slice of the search's (n_new, B, W_out) slabs.  The ranges of W_in, W_out, n_valid and
+    W_in * n_valid are the library's to refuse (NativeError, nothing launched)."""
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise nat.NativeError("beam_step: logits must be a (B * W_in, V) float32 tensor with contiguous rows")
+    rows, V = logits.shape
+    if scores_in.dim() != 2 or scores_in.dtype != torch.float32 or not scores_in.is_contiguous():
+        raise nat.NativeError("beam_step: scores_in must be a contiguous (B, W_in) float32 tensor")
+    B, W_in = scores_in.shape
+    if B * W_in != rows or (rows > 1 and logits.stride(0) < V):
+        raise nat.NativeError(f"beam_step: {rows} logits rows (stride {logits.stride(0)}) do not match scores_in "
+                              f"{tuple(scores_in.shape)}")
+    n_out = scores_out.numel()
+    if B == 0 or n_out % B:
+        raise nat.NativeError(f"beam_step: scores_out holds {n_out} elements, no multiple of B = {B}")
+    for nm, t, dt in (("scores_out", scores_out, torch.float32), ("parent_out", parent_out, torch.int32),
+                      ("token_out", token_out, torch.int64), ("logp_out", logp_out, torch.float32)):
+        if t.dtype != dt or t.numel() != n_out or not t.is_contiguous():
+            raise nat.NativeError(f"beam_step: {nm} must be a contiguous {dt} tensor of B * W_out = {n_out} elements")
+    _chk_i32_counter(bad_count, "beam_step")
+    a = nat.BeamArgs()
+    a.logits, a.ldl, a.B, a.W_in, a.W_out = ptr(logits), max(logits.stride(0), V), B, W_in, n_out // B
+    a.V, a.n_valid, a.scores_in = V, V if n_valid is None else int(n_valid), ptr(scores_in)
+    a.scores_out, a.parent_out, a.token_out, a.logp_out = ptr(scores_out), ptr(parent_out), ptr(token_out), ptr(logp_out)
+    a.bad_count = ptr(bad_count)
+    call("aw_beam_step", ctypes.byref(a), stream_ptr(stream))
+
+
+def beam_cache_table(cache_sets):
+    """The device pointer tables aw_beam_gather reads: row i holds the base pointers of cache_sets[i], a list of one
+    (rows, Tmax, width) tensor per decoder block.  Built once per search; the sets must outlive its use."""
+    first = cache_sets[0][0]
+    for kv in cache_sets:
+        if len(kv) != len(cache_sets[0]):
+            raise nat.NativeError("beam_cache_table: every cache set needs one tensor per block")
+        for t in kv:
+            if t.dim() != 3 or t.dtype != first.dtype or t.shape[1:] != first.shape[1:] or not t.is_contiguous():
+                raise nat.NativeError("beam_cache_table: caches must be contiguous (rows, Tmax, width) tensors of one "
+                                      "dtype, Tmax and width")
+    return torch.tensor([[ptr(t) for t in kv] for kv in cache_sets], dtype=torch.int64, device=first.device)
+
+
+def beam_gather(src_tab, dst_tab, B, W_in, parent, Tmax, n_pos, width, dtype, bad_count, stream=None):
+    """aw_beam_gather: dst[k][b * W_out + j, :n_pos] = src[k][b * W_in + parent[b, j], :n_pos] for every block k in one
+    launch; see include/arcweld_amd.h.  src_tab / dst_tab: rows of ``beam_cache_table`` (int64 device tensors of one
+    pointer per block) whose caches hold B * W_in and B * W_out rows of (Tmax, width) ``dtype`` elements; parent (B,
+    W_out) int32.  A parent outside [0, W_in) zero-fills its row and adds 1 to bad_count."""
+    for nm, t in (("src_tab", src_tab), ("dst_tab", dst_tab)):
+        if t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous() or t.numel() != src_tab.numel():
+            raise nat.NativeError(f"beam_gather: {nm} must be a contiguous 1-d int64 tensor, one pointer per block")
+    if parent.dtype != torch.int32 or parent.dim() != 2 or parent.shape[0] != B or not parent.is_contiguous():
+        raise nat.NativeError(f"beam_gather: parent must be a contiguous ({B}, W_out) int32 tensor")
+    _chk_i32_counter(bad_count, "beam_gather")
+    call("aw_beam_gather", ptr(src_tab), ptr(dst_tab), src_tab.numel(), int(B), int(W_in), parent.shape[1], ptr(parent),
+         int(Tmax), int(n_pos), int(width), dtype_code(dtype), ptr(bad_count), stream_ptr(stream))
+
+
+def beam_backtrack(parent, token, logp, ids_out, col0, logp_out, bad_count, stream=None):
+    """aw_beam_backtrack: the slabs parent (int32), token (int64), logp (f32), each (n_new, B, W), walked back into
+    ids_out[:, :, col0:col0 + n_new] ((B, R, >= col0 + n_new) int64) and logp_out ((B, R, n_new) f32) for the final
+    beams j < R; see include/arcweld_amd.h."""
+    if parent.dim() != 3:
+        raise nat.NativeError("beam_backtrack: the slabs must be (n_new, B, W)")
+    n_new, B, W = parent.shape
+    for nm, t, dt in (("parent", parent, torch.int32), ("token", token, torch.int64), ("logp", logp, torch.float32)):
+        if t.dtype != dt or tuple(t.shape) != (n_new, B, W) or not t.is_contiguous():
+            raise nat.NativeError(f"beam_backtrack: {nm} must be a contiguous {dt} tensor of shape {(n_new, B, W)}")
+    if (ids_out.dtype != torch.int64 or ids_out.dim() != 3 or ids_out.shape[0] != B or not ids_out.is_contiguous()
+            or not 0 <= col0 <= ids_out.shape[2] - n_new):
+        raise nat.NativeError(f"beam_backtrack: ids_out must be a contiguous (B, R, >= {col0} + {n_new}) int64 tensor")
+    R = ids_out.shape[1]
+    if logp_out.dtype != torch.float32 or tuple(logp_out.shape) != (B, R, n_new) or not logp_out.is_contiguous():
+        raise nat.NativeError(f"beam_backtrack: logp_out must be a contiguous float32 tensor of shape {(B, R, n_new)}")
+    _chk_i32_counter(bad_count, "beam_backtrack")
+    call("aw_beam_backtrack", ptr(parent), ptr(token), ptr(logp), n_new, B, W, R, ptr(ids_out), ids_out.shape[2],
+         int(col0), ptr(logp_out), ptr(bad_count), stream_ptr(stream))
+
+
 def score_rows(logits, targets, seq_rows, groups, group_rows, logp, rank, entropy, group_nll, bad_count, n_valid=None,
                stream=None):
     """aw_score_rows: teacher-forced scores of logits (n_seq * seq_rows, V) f32 (rows may be padded: stride(0) >= V)

@@ -13,6 +13,9 @@ where x_hat[:, :prompt_cycles*200] is the VQ-VAE's reconstruction of the prompt.
 (``--top-k`` / ``--min-p`` / ``--top-p`` filtered, ``--temperature`` scaled) distribution with ``--seed``; the default
 is greedy.  ``--logp`` adds gen_logp, gen_logq (n, (n_cycles - prompt_cycles)*S) and gen_cycle_nll (n, n_cycles -
 prompt_cycles): the generated ids' log-probabilities on the scale of score_welding_cycles.py (continue_cycles).
+``--num-beams W`` searches for the most probable continuation with a beam of width W instead (it excludes the sampling
+flags); ids / x_hat are then the best hypothesis, and the ``--num-return`` R best ones are added as beam_ids
+(n, R, n_cycles*S), beam_scores (n, R) -- their log-probabilities, best first -- and beam_x_hat (n, R, n_cycles*200, 2).
 """
 import argparse
 import logging as log
@@ -42,6 +45,9 @@ def parser():
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--logp', action=argparse.BooleanOptionalAction, default=False,
                    help="also store the generated ids' log-probabilities")
+    p.add_argument('--num-beams', type=int, default=None,
+                   help="beam search of this width (1..32) instead of greedy decoding or sampling")
+    p.add_argument('--num-return', type=int, default=1, help="hypotheses stored per sequence (1..num_beams)")
     p.add_argument('--precision', choices=["fp32", "bf16"], default="fp32",
                    help="MFMA operand dtype (bf16: opt-in, fp32 accumulation)")
     p.add_argument('--out', type=str, default="generated_cycles.npz")
@@ -83,8 +89,11 @@ def main(hparams):
     prompt = load_prompts(hparams, vqvae.seq_len, dev)
     out = continue_cycles(vqvae, decoder, prompt, hparams.n_cycles, do_sample=bool(hparams.do_sample),
                           top_k=hparams.top_k, temperature=hparams.temperature, seed=hparams.seed,
-                          top_p=hparams.top_p, min_p=hparams.min_p, return_logp=bool(hparams.logp))
-    extra = {k: out[k].cpu().numpy() for k in ("gen_logp", "gen_logq", "gen_cycle_nll") if k in out}
+                          top_p=hparams.top_p, min_p=hparams.min_p, return_logp=bool(hparams.logp),
+                          **({} if hparams.num_beams is None else
+                             dict(num_beams=hparams.num_beams, num_return=hparams.num_return)))
+    extra = {k: out[k].cpu().numpy() for k in ("gen_logp", "gen_logq", "gen_cycle_nll", "beam_ids", "beam_scores",
+                                               "beam_x_hat") if k in out}
     np.savez(hparams.out, prompt=prompt.cpu().numpy(), ids=out["ids"].cpu().numpy(),
              x_hat=out["x_hat"].cpu().numpy(), **extra)
     log.info(f"wrote {hparams.out}: {tuple(out['ids'].shape)} ids, {tuple(out['x_hat'].shape)} signals")

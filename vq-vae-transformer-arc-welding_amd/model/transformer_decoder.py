@@ -356,6 +356,82 @@ class MyTransformerDecoder(LightningModule):
             raise RuntimeError(f"generate_ids: {nbad} sampling steps met logits with a NaN or no finite value")
         return (out, lp) if return_logp else out
 
+    @torch.no_grad()
+    def beam_search_ids(self, x, n_new, num_beams, valid_ids=None, num_return=1):
+        """Fixed-length beam search: ids (B, L0) int64 -> {"ids": (B, num_return, L0 + n_new) int64, "scores":
+        (B, num_return) f32, "logp": (B, num_return, n_new) f32}, the num_return most probable continuations the search
+        found, best first.  logp holds each generated id's log-probability under the model over the allowed ids -- the
+        scale of ``score_ids(ids, valid_ids)`` and of ``generate_ids(return_logp=True)`` --, scores its running sum as
+        the search accumulated it (the sum of logp up to f32 rounding).
+
+        num_beams in 1..32 beams are kept per sequence, and num_beams * (the number of allowed ids) may not exceed 16384
+        (a sequence's candidates are ranked in one workgroup's LDS); 1 <= num_return <= num_beams.  valid_ids and the
+        length rule L0 + n_new <= seq_len are those of ``generate_ids``.  Every hypothesis has exactly n_new new ids:
+        with ``valid_ids = n_classes - 2`` no end token can be produced, so there is no length penalty and no early
+        finish.  Candidates are ranked by score descending, equal scores by the lower (beam, id) pair, so the result is
+        the same on every call.  num_beams = 1 returns the ids of greedy ``generate_ids``.  n_new = 0 returns the prompt
+        repeated, zero scores and an empty logp.  When fewer than num_return different continuations exist
+        (n_valid ** n_new < num_return) the tail carries score -inf (and ids that repeat other rows' prefixes).
+
+        One prefill on B rows, then per token one cached decode step on B * num_beams rows, ONE aw_beam_step launch
+        (log-softmax, add the beam scores, keep the best num_beams of num_beams * n_valid candidates, written into
+        per-step slabs) and ONE aw_beam_gather launch that reorders all blocks' KV caches by the survivors' parents
+        into a second cache set (the two sets swap; the operand copies of the weights are made once and shared); one
+        aw_beam_backtrack launch at the end turns the slabs into hypotheses.  No torch op per token beyond
+        ``forward_cached``'s own.  Logits with a NaN or no finite value raise RuntimeError at the end."""
+        if x.dim() != 2 or x.dtype != torch.int64:
+            raise ValueError("beam_search_ids expects int64 ids of shape (B, L0)")
+        B, L0 = x.shape
+        n_new = int(n_new)
+        if L0 < 1 or n_new < 0 or L0 + n_new > self.seq_len:
+            raise ValueError(f"beam_search_ids: prompt length {L0} + n_new {n_new} must lie in 1..seq_len = "
+                             f"{self.seq_len}")
+        n_valid = self._n_valid(valid_ids, "beam_search_ids")
+        W, R = int(num_beams), int(num_return)
+        if not 1 <= W <= K.nat.BEAM_MAX_W:
+            raise ValueError(f"beam_search_ids: num_beams = {num_beams} outside 1..{K.nat.BEAM_MAX_W}")
+        if not 1 <= R <= W:
+            raise ValueError(f"beam_search_ids: num_return = {num_return} outside 1..num_beams = {W}")
+        if W * n_valid > K.nat.SAMPLE_MAX_V:
+            raise ValueError(f"beam_search_ids: num_beams * allowed ids = {W} * {n_valid} exceeds the "
+                             f"{K.nat.SAMPLE_MAX_V} candidates one workgroup ranks")
+        dev = x.device
+        ids = x[:, None, :].expand(B, R, L0)
+        if n_new == 0:
+            return {"ids": ids.contiguous(), "scores": torch.zeros(B, R, device=dev),
+                    "logp": torch.empty(B, R, 0, device=dev)}
+        out = torch.empty(B, R, L0 + n_new, dtype=torch.int64, device=dev)
+        out[:, :, :L0] = ids
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        score = torch.empty(n_new, B, W, device=dev)
+        logp = torch.empty(n_new, B, W, device=dev)
+        parent = torch.empty(n_new, B, W, dtype=torch.int32, device=dev)
+        token = torch.empty(n_new, B, W, dtype=torch.int64, device=dev)
+        prompt = engine.KVCache(self, B, self.seq_len)       # as generate_ids: the same prefill, the same logits
+        width = 2 * self.d_model
+
+        def step(i, logits, scores_in):
+            K.beam_step(logits, scores_in, score[i], parent[i], token[i], logp[i], bad, n_valid=n_valid)
+
+        step(0, engine.forward_cached(self, x, prompt, 0), torch.zeros(B, 1, device=dev))
+        if n_new > 1:
+            cur, nxt = (engine.KVCache(self, B * W, self.seq_len, share=prompt) for _ in range(2))
+            tab = list(K.beam_cache_table([prompt.kv, cur.kv, nxt.kv]))      # built once: three rows of pointers
+            K.beam_gather(tab[0], tab[1], B, 1, parent[0], self.seq_len, L0, width, prompt.T_, bad)
+            src, dst = 1, 2
+            for i in range(1, n_new):
+                pos = L0 + i                                 # the column this step fills
+                step(i, engine.forward_cached(self, token[i - 1].view(B * W, 1), cur, pos - 1), score[i - 1])
+                if i < n_new - 1:
+                    K.beam_gather(tab[src], tab[dst], B, W, parent[i], self.seq_len, pos, width, prompt.T_, bad)
+                    cur, nxt, src, dst = nxt, cur, dst, src
+        lp = torch.empty(B, R, n_new, device=dev)
+        K.beam_backtrack(parent, token, logp, out, L0, lp, bad)
+        nbad = int(bad.item())
+        if nbad:
+            raise RuntimeError(f"beam_search_ids: {nbad} steps met logits with a NaN or no finite value")
+        return {"ids": out, "scores": score[n_new - 1, :, :R].contiguous(), "logp": lp}
+
     def _check_scoring(self, x, who):
         """The argument checks of score_ids / score_groups, before any launch."""
         if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.int64:
