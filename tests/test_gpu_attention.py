@@ -145,16 +145,8 @@ def _dropout_keep(seed, B, nh, T, p):
     """The kernels' counter-based mask (common.h aw_hash_group / aw_dropout_scale), restated in numpy: element
     e = ((b*nh + h)*T + i)*T + j is dropped iff its 16-bit slice of splitmix64(seed, e >> 2) < round(p * 65536)."""
     import numpy as np
-    M = np.uint64(0xFFFFFFFFFFFFFFFF)
-    e = np.arange(B * nh * T * T, dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        z = np.uint64(seed) + (e // np.uint64(4) + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        z = z ^ (z >> np.uint64(31))
-    u = (z >> (np.uint64(16) * (e & np.uint64(3)))) & np.uint64(0xFFFF)
-    keep = u >= np.uint64(int(p * 65536 + 0.5))
-    del M
+    from kernel_refs import dropout_keep
+    keep = dropout_keep(seed, np.arange(B * nh * T * T, dtype=np.uint64), p)
     return torch.tensor(keep.reshape(B, nh, T, T))
 
 

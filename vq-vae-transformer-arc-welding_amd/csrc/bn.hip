@@ -11,23 +11,43 @@
 namespace {
 
 constexpr int BN_ROWS = 64;   // rows of one group per statistics block
+constexpr int BN_LOADS = 16;  // rows whose loads bn_stats_kernel issues together
 
-// sums[0][g][c] += sum h, sums[1][g][c] += sum h^2 over rows r = g + G*k
+// sums[0][g][c] += sum h, sums[1][g][c] += sum h^2 over rows r = g + G*k.
+// Both sums run in f64 from the first row on: the finalize forms E[h^2] - mean^2, which cancels (mean/std)^2 of the
+// leading digits, so 64-row f32 partial sums of h and h^2 left a normalised-output error of 2.4e-4 at mean/std = 30
+// and 2.3e-2 at mean/std = 300 (measured, N = 512; torch's fp32 batch_norm: 3e-6 and 2e-5).  The f32 x f32 product is
+// exact in f64, so E[h^2] and the mean are now correct to f64 rounding (7.8e-7 and 9e-6 on the same inputs:
+// tests/test_bn_kernels_gpu.py); the kernel is bound by its loads (one f64 add + one f64 FMA per 4-byte load).
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ h, int64_t N, int H, int G,
                                                        double* __restrict__ sums) {
   const int g = blockIdx.y;
   const int64_t per = (N - g + G - 1) / G;          // rows of group g
   const int64_t k0 = (int64_t)blockIdx.x * BN_ROWS, k1 = min(per, k0 + BN_ROWS);
   for (int c = threadIdx.x; c < H; c += blockDim.x) {
-    float s = 0.f, q = 0.f;
-    for (int64_t k = k0; k < k1; ++k) {
-      const float v = h[(g + k * G) * H + c];
-      s += v;
-      q = fmaf(v, v, q);
+    double s = 0.0, q = 0.0;
+    int64_t k = k0;
+    // BN_LOADS rows' loads in flight at a time (the plain row loop compiled to load - wait - add, one row's latency
+    // after the other); the additions keep the row order
+    for (; k + BN_LOADS <= k1; k += BN_LOADS) {
+      float v[BN_LOADS];
+#pragma unroll
+      for (int u = 0; u < BN_LOADS; ++u) v[u] = h[(g + (k + u) * G) * H + c];
+#pragma unroll
+      for (int u = 0; u < BN_LOADS; ++u) {
+        const double d = (double)v[u];
+        s += d;
+        q = fma(d, d, q);
+      }
+    }
+    for (; k < k1; ++k) {
+      const double d = (double)h[(g + k * G) * H + c];
+      s += d;
+      q = fma(d, d, q);
     }
     if (k1 > k0) {
-      atomicAdd(sums + (int64_t)g * H + c, (double)s);
-      atomicAdd(sums + ((int64_t)G + g) * H + c, (double)q);
+      atomicAdd(sums + (int64_t)g * H + c, s);
+      atomicAdd(sums + ((int64_t)G + g) * H + c, q);
     }
   }
 }
