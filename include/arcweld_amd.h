@@ -749,6 +749,49 @@ int aw_score_rows(const float* logits, int64_t ldl, int V, int n_valid, const in
 int aw_window_sqerr(const float* a, const float* b, const int64_t* idx, int64_t n_idx_rows, int64_t windows,
                     int rows_per_window, int width, float* out, int* bad_count, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ ensemble forecasts
+ * Pointwise statistics over an ensemble in one launch (arcweld.generate.forecast_cycles), and with a truth the forecast's
+ * score against it.  x: (G, N, M) f32 contiguous -- G groups (prompts), N samples, M points each.  Per point (g, m) over
+ * its samples x_1..x_N, with x_(1) <= ... <= x_(N) the same values sorted ascending (values move, no bit changes):
+ *   - mean[g, m]     = (sum_i x_i) / N, the sum in f64 in index order, rounded once to f32;
+ *   - std[g, m]      = sqrt(sum_i (x_i - mean64)^2 / (N - 1)) in f64, rounded once (torch.std's default); 0 for N = 1;
+ *   - quant[g, k, m] = numpy's default "linear" quantile of q[k]: h = (N - 1) * q[k] in f64, lo = floor(h), hi =
+ *     min(lo + 1, N - 1), value = x_(lo+1) + (float)(h - lo) * (x_(hi+1) - x_(lo+1)) in f32 (one subtract, one fused
+ *     multiply-add); an integral h gives the order statistic itself bit for bit (q = 0, q = 1, N = 1 included);
+ *   - with y (G, M), the ensemble CRPS of the point, in f64 from the f32 values:
+ *       c = (1/N) sum_i |x_i - y| - (1/N^2) sum_{i=1..N} (2 i - N - 1) x_(i)
+ *     (= mean |x - y| - 0.5 * mean_{i,j} |x_i - x_j|, the pair term from the sorted samples in O(N));
+ *   - crps[g, s]  = the mean of c over the `seg` points of segment s (points [s * seg, (s + 1) * seg): one cycle),
+ *     rounded once to f32;
+ *   - cover[g, s] = the number of the segment's points with quant[g, 0, m] <= y <= quant[g, Q-1, m] -- the f32
+ *     quantiles exactly as stored --, divided by seg.
+ * Segment sums run in one fixed order: a thread adds its points in index order into an f64 partial, then a fixed tree
+ * over the workgroup; no floating-point atomic, the same bits on every launch.
+ * A point is bad when one of its samples is non-finite, or when y is given and non-finite there: it stores NaN in mean,
+ * std and every quant, makes its segment's crps and cover NaN and adds 1 to *bad_count (a device int the caller zeroed;
+ * one integer atomic per workgroup at most).
+ * q is a HOST array of Q probabilities (they travel in the kernel arguments).  mean, std may each be NULL (skipped);
+ * quant is required when Q > 0; y NULL: crps and cover must be NULL; crps, cover may each be NULL.
+ * One 256-thread workgroup per (g, s); a thread's N samples are sorted in its own LDS column, sample i at float index
+ * i * 256 + thread (N KiB of LDS per workgroup, conflict-free).
+ * AW_ERR_ARG and no launch: N outside 1..AW_ENSEMBLE_MAX_N, Q outside 0..AW_ENSEMBLE_MAX_Q, a q outside [0, 1] or NaN,
+ * seg < 1, M % seg != 0, cover with Q < 2, crps or cover without y, quant NULL with Q > 0, G * M / seg >= 2^31.
+ * G == 0 or M == 0: AW_OK, nothing launched. */
+#define AW_ENSEMBLE_MAX_N 64
+#define AW_ENSEMBLE_MAX_Q 8
+typedef struct {
+  const float* x;  int G, N; int64_t M;
+  const float* q;  int Q;
+  float* mean; float* std;
+  float* quant;
+  const float* y;
+  int64_t seg;
+  float* crps;
+  float* cover;
+  int* bad_count;
+} aw_ensemble_args;
+int aw_ensemble_stats(const aw_ensemble_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,23 @@ class BeamArgs(ctypes.Structure):
                 ("bad_count", c_p)]
 
 
+ENSEMBLE_MAX_N = 64   # AW_ENSEMBLE_MAX_N
+ENSEMBLE_MAX_Q = 8    # AW_ENSEMBLE_MAX_Q
+
+
+class EnsembleArgs(ctypes.Structure):
+    """aw_ensemble_args (include/arcweld_amd.h)."""
+    _fields_ = [("x", c_p), ("G", c_int), ("N", c_int), ("M", c_i64),
+                ("q", ctypes.POINTER(c_f)), ("Q", c_int),
+                ("mean", c_p), ("std", c_p),
+                ("quant", c_p),
+                ("y", c_p),
+                ("seg", c_i64),
+                ("crps", c_p),
+                ("cover", c_p),
+                ("bad_count", c_p)]
+
+
 # name -> argtypes (every entry returns int status except aw_last_error)
 SIGNATURES = {
     "aw_version": [],
@@ -220,6 +237,7 @@ SIGNATURES = {
     "aw_beam_backtrack": [c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_i64, c_i64, c_p, c_p, c_p],
     "aw_score_rows": [c_p, c_i64, c_int, c_int, c_p, c_i64, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p],
     "aw_window_sqerr": [c_p, c_p, c_p, c_i64, c_i64, c_int, c_int, c_p, c_p, c_p],
+    "aw_ensemble_stats": [ctypes.POINTER(EnsembleArgs), c_p],
 }
 
 RET_I64 = {"aw_gemm_workspace", "aw_wgrad_batch_workspace", "aw_res_dropout_masks_bytes"}

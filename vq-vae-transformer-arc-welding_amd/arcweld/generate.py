@@ -10,6 +10,10 @@ and the ranked hypotheses come back beside the best one.
 ``score_cycles`` is the mirror for cycles that were measured: the same two models, the same id layout and the same
 restriction to the codebook ids, but the ids come from the encoder and the Transformer only says how likely each one
 was (aw_score_rows), beside the VQ-VAE's own reconstruction and quantisation errors per cycle (aw_window_sqerr).
+
+``forecast_cycles`` draws many continuations of one prompt at once (MyTransformerDecoder.sample_ids: one prefill, the
+cache fanned out by aw_beam_gather) and reduces their decoded signals on the device to a mean, a spread, quantile bands
+and -- against the cycles that were measured afterwards -- a CRPS and a band coverage per cycle (aw_ensemble_stats).
 """
 from __future__ import annotations
 
@@ -83,6 +87,89 @@ def continue_cycles(vqvae, decoder, x_prompt, n_cycles, do_sample=False, top_k=N
     if lp is not None:
         res.update(gen_logp=lp["logp"], gen_logq=lp["logq"],
                    gen_cycle_nll=-lp["logp"].view(ids.shape[0], n_cycles - c, S).sum(-1))
+    return res
+
+
+@torch.no_grad()
+def forecast_cycles(vqvae, decoder, x_prompt, n_cycles, num_samples, quantiles=(0.05, 0.5, 0.95), x_true=None,
+                    top_k=None, top_p=None, min_p=None, temperature=1.0, seed=0, dtype=None):
+    """An ensemble forecast: N = num_samples (1..32) sampled continuations of every prompt, the pointwise spread of
+    their signals, and -- when the cycles that followed were measured -- the forecast's score against them.  With
+    x_prompt (B, c*L, C) f32, 1 <= c < n_cycles, f = n_cycles - c forecast cycles and Q quantiles:
+
+      ids (B, N, n_cycles*S) int64          x_prompt_hat (B, c*L, C)          x_hat (B, N, f*L, C)
+      sample_cycle_nll (B, N, f)            mean, std (B, f*L, C)             quantiles (B, Q, f*L, C)
+      with x_true (B, f*L, C) f32:          crps (B, f)                       coverage (B, f)   (needs Q >= 2)
+
+    ids: the prompt's ids followed by each sample's f*S drawn ones (MyTransformerDecoder.sample_ids: one prefill per
+    prompt, the cache fanned out to B*N rows; top_k / top_p / min_p / temperature / seed as in ``continue_cycles``
+    with do_sample).  x_prompt_hat is the VQ-VAE's reconstruction of the prompt, decoded once; x_hat the generated
+    cycles of all samples, one ``decode_ids`` pass.  sample_cycle_nll is -logp summed per cycle, on ``score_cycles``'
+    cycle_nll scale, from the launches that drew the ids.  mean / std (unbiased) / quantiles (numpy's "linear"
+    rule; ``quantiles`` ascending in [0, 1], at most 8) are taken over the N samples at every point; crps is the
+    ensemble CRPS against x_true averaged over each cycle's L*C points (in signal units: 0 is a perfect, sharp
+    forecast), coverage the share of a cycle's points whose truth lies between the first and the last quantile.  All
+    of them come from ONE aw_ensemble_stats launch (G = B, M = f*L*C, seg = L*C): no sample leaves the device.
+
+    The model-fit and prompt rules are ``continue_cycles``'; num_samples = 1 gives its sampled continuation."""
+    S = tokenize.ids_per_window(vqvae)
+    L, Kc = vqvae.seq_len, vqvae.num_embeddings
+    n_cycles = int(n_cycles)
+    if decoder.seq_len != n_cycles * S + 1 or decoder.n_classes != Kc + 2:
+        raise ValueError(f"forecast_cycles: the Transformer (seq_len {decoder.seq_len}, n_classes {decoder.n_classes}) "
+                         f"does not fit {n_cycles} cycles of this VQ-VAE: it needs seq_len = n_cycles*S + 1 = "
+                         f"{n_cycles * S + 1} and n_classes = num_embeddings + 2 = {Kc + 2}")
+    if (not isinstance(x_prompt, torch.Tensor) or x_prompt.dim() != 3 or x_prompt.shape[1] % L
+            or not L <= x_prompt.shape[1] < n_cycles * L):
+        raise ValueError(f"forecast_cycles: the prompt must be (B, c*{L}, C) with 1 <= c < n_cycles = {n_cycles}, "
+                         f"got {tuple(getattr(x_prompt, 'shape', ()))}")
+    from . import kernels as K
+    N = int(num_samples)
+    if not 1 <= N <= K.nat.BEAM_MAX_W:
+        raise ValueError(f"forecast_cycles: num_samples = {num_samples} outside 1..{K.nat.BEAM_MAX_W}")
+    qs = [float(q) for q in quantiles]
+    Q = len(qs)
+    if Q > K.nat.ENSEMBLE_MAX_Q or any(not 0.0 <= q <= 1.0 for q in qs) or any(a > b for a, b in zip(qs, qs[1:])):
+        raise ValueError(f"forecast_cycles: quantiles must be at most {K.nat.ENSEMBLE_MAX_Q} ascending probabilities "
+                         f"in [0, 1], got {tuple(quantiles)}")
+    B, C = x_prompt.shape[0], x_prompt.shape[2]
+    c = x_prompt.shape[1] // L
+    f = n_cycles - c
+    if x_true is not None:
+        if (not isinstance(x_true, torch.Tensor) or x_true.dtype != torch.float32
+                or tuple(x_true.shape) != (B, f * L, C)):
+            raise ValueError(f"forecast_cycles: x_true must be float32 {(B, f * L, C)}, the {f} cycles after the "
+                             f"prompt, got {getattr(x_true, 'dtype', type(x_true))} "
+                             f"{tuple(getattr(x_true, 'shape', ()))}")
+        if Q < 2:
+            raise ValueError("forecast_cycles: the coverage of x_true needs at least two quantiles (the band's edges), "
+                             f"got {Q}")
+    start = decoder.n_classes - 2
+    kw = {} if dtype is None else dict(dtype=dtype)          # encode_ids' own default is exact fp32
+    prompt_ids = tokenize.encode_ids(vqvae, x_prompt, **kw)
+    x = torch.cat([torch.full_like(prompt_ids[:, :1], start), prompt_ids], dim=1)
+    out, lp = decoder.sample_ids(x, f * S, N, top_k=top_k, temperature=temperature, valid_ids=start, seed=seed,
+                                 top_p=top_p, min_p=min_p, return_logp=True)
+    ids = out[:, :, 1:].contiguous()
+    x_prompt_hat = tokenize.decode_ids(vqvae, prompt_ids, dtype=dtype)
+    x_hat = tokenize.decode_ids(vqvae, ids[:, :, c * S:].reshape(B * N, f * S), dtype=dtype).view(B, N, f * L, C)
+    dev = x_hat.device
+    M = f * L * C
+    mean, std = torch.empty(B, f * L, C, device=dev), torch.empty(B, f * L, C, device=dev)
+    quant = torch.empty(B, Q, f * L, C, device=dev)
+    res = {"ids": ids, "x_prompt_hat": x_prompt_hat, "x_hat": x_hat,
+           "sample_cycle_nll": -lp["logp"].view(B, N, f, S).sum(-1), "mean": mean, "std": std, "quantiles": quant}
+    y = crps = cover = None
+    if x_true is not None:
+        y = x_true.contiguous().view(B, M)
+        crps, cover = torch.empty(B, f, device=dev), torch.empty(B, f, device=dev)
+        res.update(crps=crps, coverage=cover)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    K.ensemble_stats(x_hat.view(B, N, M), qs, mean=mean.view(B, M), std=std.view(B, M),
+                     quant=quant.view(B, Q, M) if Q else None, y=y, seg=L * C, crps=crps, cover=cover, bad_count=bad)
+    nbad = int(bad.item())
+    if nbad:
+        raise RuntimeError(f"forecast_cycles: {nbad} points hold a non-finite sample or a non-finite x_true value")
     return res
 
 

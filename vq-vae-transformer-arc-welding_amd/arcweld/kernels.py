@@ -698,6 +698,38 @@ def window_sqerr(a, b, out, bad_count, idx=None, stream=None):
          ptr(bad_count), stream_ptr(stream))
 
 
+def ensemble_stats(x, q, mean=None, std=None, quant=None, y=None, seg=None, crps=None, cover=None, bad_count=None,
+                   stream=None):
+    """aw_ensemble_stats: pointwise statistics of x (G, N, M) f32 over its N samples, and with a truth y (G, M) the
+    forecast's score per segment of ``seg`` points (None: one segment, seg = M); see include/arcweld_amd.h for the
+    semantics.  q: a sequence of Q probabilities on the host.  mean, std (G, M), quant (G, Q, M), crps, cover
+    (G, M // seg): contiguous f32, each optional except quant when Q > 0.  The ranges of N, Q, q and seg, and which
+    outputs need which inputs, are the library's to refuse (NativeError, nothing launched)."""
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise nat.NativeError("ensemble_stats: x must be a contiguous (G, N, M) float32 tensor")
+    G, N, M = x.shape
+    qs = [float(v) for v in q]
+    Q = len(qs)
+    seg = M if seg is None else int(seg)
+    n_seg = M // seg if seg >= 1 else 0        # seg < 1 or M % seg != 0: refused by the library
+    for nm, t, sh in (("mean", mean, (G, M)), ("std", std, (G, M)), ("quant", quant, (G, Q, M)), ("y", y, (G, M)),
+                      ("crps", crps, (G, n_seg)), ("cover", cover, (G, n_seg))):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != sh or not t.is_contiguous()
+                              or t.device != x.device):
+            raise nat.NativeError(f"ensemble_stats: {nm} must be a contiguous float32 tensor of shape {sh} on x's "
+                                  f"device, got {t.dtype} {tuple(t.shape)}")
+    if bad_count is None:
+        raise nat.NativeError("ensemble_stats: bad_count must be one int32 on the device")
+    _chk_i32_counter(bad_count, "ensemble_stats")
+    a = nat.EnsembleArgs()
+    qa = (nat.c_f * max(Q, 1))(*qs)
+    a.x, a.G, a.N, a.M = ptr(x), G, N, M
+    a.q, a.Q = ctypes.cast(qa, ctypes.POINTER(nat.c_f)), Q
+    a.mean, a.std, a.quant, a.y = ptr(mean), ptr(std), ptr(quant), ptr(y)
+    a.seg, a.crps, a.cover, a.bad_count = seg, ptr(crps), ptr(cover), ptr(bad_count)
+    call("aw_ensemble_stats", ctypes.byref(a), stream_ptr(stream))
+
+
 # ------------------------------------------------------------------------------------------ layouts
 def patchify(x, P, out, stream=None):
     B, L, C = x.shape

@@ -357,6 +357,78 @@ class MyTransformerDecoder(LightningModule):
         return (out, lp) if return_logp else out
 
     @torch.no_grad()
+    def sample_ids(self, x, n_new, num_samples, top_k=None, temperature=1.0, valid_ids=None, seed=0, top_p=None,
+                   min_p=None, return_logp=False):
+        """An ensemble of continuations: ids (B, L0) int64 -> (B, N, L0 + n_new) int64, N = num_samples independent
+        draws of n_new tokens per prompt; with return_logp also {"logp", "logq"}, each (B, N, n_new) f32, as
+        ``generate_ids`` defines them.  Always samples (greedy is ``generate_ids``).  num_samples in 1..32, the fan-out
+        limit of aw_beam_gather; every other argument and the length rule L0 + n_new <= seq_len are ``generate_ids``'.
+
+        Sample j of prompt b is row b * N + j of the B * N rows the token launches see, so
+        ``sample_ids(x, n_new, N, seed=s, ...)[b, j]`` equals ``generate_ids(x.repeat_interleave(N, 0), n_new,
+        do_sample=True, seed=s, ...)[b * N + j]``: the same draw counter step * (B * N) + row.
+
+        ONE prefill on the B prompt rows (not B * N); its logits rows are repeated to B * N once and ONE aw_beam_gather
+        launch (W_in = 1, a zero parent table) spreads the prompt's cache of every block over B * N rows of a second
+        cache set that shares the operand copies of the weights.  Then per token one cached decode step on B * N rows
+        and one aw_sample_next / aw_sample_next_ex launch, both writing into the preallocated result viewed as
+        (B * N, ...).  Logits with a NaN or no finite value raise RuntimeError at the end."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.int64:
+            raise ValueError("sample_ids expects int64 ids of shape (B, L0)")
+        B, L0 = x.shape
+        n_new = int(n_new)
+        if L0 < 1 or n_new < 0 or L0 + n_new > self.seq_len:
+            raise ValueError(f"sample_ids: prompt length {L0} + n_new {n_new} must lie in 1..seq_len = {self.seq_len}")
+        N = int(num_samples)
+        if not 1 <= N <= K.nat.BEAM_MAX_W:
+            raise ValueError(f"sample_ids: num_samples = {num_samples} outside 1..{K.nat.BEAM_MAX_W}")
+        n_valid = self._n_valid(valid_ids, "sample_ids")
+        k = 0 if top_k is None else int(top_k)
+        if top_k is not None and not 1 <= k <= n_valid:
+            raise ValueError(f"sample_ids: top_k = {top_k} outside 1..{n_valid} allowed ids")
+        if not (temperature > 0 and math.isfinite(temperature)):
+            raise ValueError(f"sample_ids: temperature must be positive and finite, got {temperature}")
+        if top_p is not None and not 0.0 < top_p <= 1.0:
+            raise ValueError(f"sample_ids: top_p must lie in (0, 1], got {top_p}")
+        if min_p is not None and not 0.0 <= min_p < 1.0:
+            raise ValueError(f"sample_ids: min_p must lie in [0, 1), got {min_p}")
+        ex = top_p is not None or min_p is not None or return_logp
+        dev = x.device
+        out = torch.empty(B, N, L0 + n_new, dtype=torch.int64, device=dev)
+        out[:, :, :L0] = x[:, None, :]
+        lp = {nm: torch.empty(B, N, n_new, device=dev) for nm in ("logp", "logq")} if return_logp else None
+        if n_new == 0:
+            return (out, lp) if return_logp else out
+        rows = out.view(B * N, L0 + n_new)
+        lp_rows = {nm: t.view(B * N, n_new) for nm, t in lp.items()} if lp else None
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+
+        def pick(i, logits):
+            if ex:
+                K.sample_next_ex(logits, rows, L0 + i, bad, n_valid=n_valid, top_k=k,
+                                 top_p=1.0 if top_p is None else top_p, min_p=0.0 if min_p is None else min_p,
+                                 inv_temperature=1.0 / temperature, do_sample=True, seed=seed, step=i,
+                                 logp_out=lp_rows and lp_rows["logp"], logq_out=lp_rows and lp_rows["logq"], col_lp=i)
+            else:
+                K.sample_next(logits, rows, L0 + i, bad, n_valid=n_valid, top_k=k, inv_temperature=1.0 / temperature,
+                              do_sample=True, seed=seed, step=i)
+
+        prompt = engine.KVCache(self, B, self.seq_len)       # as generate_ids: the same prefill, the same logits
+        pick(0, engine.forward_cached(self, x, prompt, 0).repeat_interleave(N, dim=0))
+        if n_new > 1:
+            cur = engine.KVCache(self, B * N, self.seq_len, share=prompt)
+            tab = K.beam_cache_table([prompt.kv, cur.kv])
+            K.beam_gather(tab[0], tab[1], B, 1, torch.zeros(B, N, dtype=torch.int32, device=dev), self.seq_len, L0,
+                          2 * self.d_model, prompt.T_, bad)
+            for i in range(1, n_new):
+                pos = L0 + i                                 # the column this step fills
+                pick(i, engine.forward_cached(self, rows[:, pos - 1:pos], cur, pos - 1))
+        nbad = int(bad.item())
+        if nbad:
+            raise RuntimeError(f"sample_ids: {nbad} sampling steps met logits with a NaN or no finite value")
+        return (out, lp) if return_logp else out
+
+    @torch.no_grad()
     def beam_search_ids(self, x, n_new, num_beams, valid_ids=None, num_return=1):
         """Fixed-length beam search: ids (B, L0) int64 -> {"ids": (B, num_return, L0 + n_new) int64, "scores":
         (B, num_return) f32, "logp": (B, num_return, n_new) f32}, the num_return most probable continuations the search
