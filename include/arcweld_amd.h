@@ -180,7 +180,23 @@ int aw_wgrad_set_spin_limit(int polls);
  * and tail_colstats (f64, 2 * H, may be NULL) += the column sums of v and v * v over the rows < N and the tail_k1
  * taps, from the f32 values before the bf16 rounding -- what aw_gemm with bias_mod = stats_mod = H computes on
  * a[R-1] and the [tail_k1 * H][H] operand copy, without the launch and without reading x_R back.  a[R-1] is still
- * stored.  (N + 64) * tail_k1 * H * 2 < 2^31; tail_y 16-B aligned. */
+ * stored.  (N + 64) * tail_k1 * H * 2 < 2^31; tail_y 16-B aligned.
+ * Forward sep tail (taps = 1 only, sep_d = 64; all-zero sep fields = none): the SepCNNBlock conv (H -> sep_d, one tap
+ * per token) that follows the encoder stack, run on x_R while it is still in LDS:
+ *   sep_z[row][c] = x_R[row] . sep_w[c] + sep_bias[c]                        (sep_z: [N][sep_d] f32, rows < N only)
+ * with sep_w the [sep_d][H] bf16 operand copy ([out][in], not packed) and sep_bias f32 -- what aw_gemm computes from
+ * a[R-1] with that operand and bias, bit for bit, without the launch and without reading x_R back.  a[R-1] is still
+ * stored.  sep_w and sep_z 16-B aligned.
+ * Forward head (head_k = 64 with taps = 3, 32 with taps = 1; all-zero head fields = none): the conv that makes x_0 runs
+ * in the launch, and x0 / a0 become outputs (either may be NULL: not stored):
+ *   x0[row][c] = bf16(v),  a0[row][c] = bf16(GELU(v)),  v = in[row] . head_w[c] + head_bias[c]
+ * -- what aw_gemm with c2_mode = 1 writes from the same operands, bit for bit.  head_w: the [H][head_k] bf16 operand
+ * copy ([out][in], not packed), head_bias f32.
+ *   taps = 3: the decoder's 1x1 conv; in = head_in, the [N][64] bf16 quantized rows.
+ *   taps = 1: patchify + the patch embed; head_in = the f32 windows [N / S][head_L][head_C], S = head_L head_C /
+ *             head_P tokens per window, in[row] = the row aw_patchify makes (head_P <= 32 elements, zero-padded to
+ *             32), also stored to head_patches ([N][32] bf16, 8-B aligned, may be NULL).
+ * head_w and (taps = 3) head_in 16-B aligned. */
 #define AW_RES_CHAIN_MAX 16
 #define AW_RES_TAIL_MAX 8
 typedef struct {
@@ -207,6 +223,16 @@ typedef struct {
   const float* tail_bias;
   void* tail_y;
   double* tail_colstats;
+  int sep_d;
+  const void* sep_w;
+  const float* sep_bias;
+  float* sep_z;
+  int head_k;
+  const void* head_in;
+  const void* head_w;
+  const float* head_bias;
+  void* head_patches;
+  int head_L, head_C, head_P;
 } aw_res_chain_fwd_args;
 typedef struct {
   int64_t N;

@@ -19,10 +19,11 @@ import os
 import sys
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REAL = {"res_chain_ok", "convt_tail_ok", "head_bf16_ok", "wgrad_issue", "wgrad_batch_ok", "attn_flops"}
+REAL = {"res_chain_ok", "convt_tail_ok", "sep_tail_ok", "chain_head_ok", "head_bf16_ok", "wgrad_issue", "wgrad_batch_ok", "attn_flops"}
 PATHS = ("fused_train_step", "autograd", "eval", "encode", "encoder[0]", "decoder[1]", "resblock")
 ENV = ("ARCWELD_ENC_CHAIN", "ARCWELD_DEC_CHAIN", "ARCWELD_RESID_F32", "ARCWELD_HEAD_BF16", "ARCWELD_CHAIN_STORE",
-       "ARCWELD_WGRAD_BATCH", "ARCWELD_OPERANDS", "ARCWELD_CONVT_TAIL")
+       "ARCWELD_WGRAD_BATCH", "ARCWELD_OPERANDS", "ARCWELD_CONVT_TAIL", "ARCWELD_SEP_TAIL",
+       "ARCWELD_CHAIN_HEAD")
 
 
 class Recorder:

@@ -82,7 +82,10 @@ class ResChainFwdArgs(ctypes.Structure):
                 ("drop_p", c_f), ("drop_seed", ctypes.c_uint64 * _E), ("seed_ptr", c_p), ("store_policy", c_int),
                 ("drop_masks", c_p),
                 ("tail_k1", c_int), ("tail_w", c_p * RES_TAIL_MAX), ("tail_bias", c_p), ("tail_y", c_p),
-                ("tail_colstats", c_p)]
+                ("tail_colstats", c_p),
+                ("sep_d", c_int), ("sep_w", c_p), ("sep_bias", c_p), ("sep_z", c_p),
+                ("head_k", c_int), ("head_in", c_p), ("head_w", c_p), ("head_bias", c_p), ("head_patches", c_p),
+                ("head_L", c_int), ("head_C", c_int), ("head_P", c_int)]
 
 
 class ResChainBwdArgs(ctypes.Structure):

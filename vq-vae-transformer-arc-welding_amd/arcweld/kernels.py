@@ -308,8 +308,23 @@ def convt_tail_ok():
     return os.environ.get("ARCWELD_CONVT_TAIL", "1") != "0"
 
 
+def sep_tail_ok():
+    """The encoder chain may run the sep conv as its tail (res_chain_fwd(sep=...)).  ARCWELD_SEP_TAIL=0 keeps the sep
+    conv's own GEMM launch (A/B runs, and the tests that compare the two)."""
+    import os
+    return os.environ.get("ARCWELD_SEP_TAIL", "1") != "0"
+
+
+def chain_head_ok():
+    """The chains may run the conv that makes their x_0 as their head (res_chain_fwd(head=...)): the decoder's 1x1
+    conv, and patchify + the patch embed.  ARCWELD_CHAIN_HEAD=0 keeps those launches (A/B runs, and the tests that
+    compare the two)."""
+    import os
+    return os.environ.get("ARCWELD_CHAIN_HEAD", "1") != "0"
+
+
 def res_chain_fwd(a0, x0, w1, w2, b1, b2, dh, a1, dx, a, drop=(0.0, None), seed_ptr=None, masks=None, taps=1, seg=16,
-                  stream=None, tail=None):
+                  stream=None, tail=None, sep=None, head=None):
     """One aw_res_chain_fwd launch over the R = len(w1) ResBlocks (see include/arcweld_amd.h).
 
     a0 / x0: (N, H) bf16; w1 / w2: R packed weight copies (res_pack_weights); b1 / b2: R f32 biases; dh / a1 / dx / a:
@@ -319,8 +334,16 @@ def res_chain_fwd(a0, x0, w1, w2, b1, b2, dh, a1, dx, a, drop=(0.0, None), seed_
 
     tail (taps 3 only) = (wt, bias, Y, colstats): the un-patch ConvT on x_R inside the launch -- wt: its k1 matrices
     [out][in], each packed as a 1-tap forward copy (res_pack_weights(..., job_taps=)), bias: (H,) f32, Y: (N, k1 H)
-    bf16, colstats: (2 H,) f64 accumulators or None."""
-    N, H = a0.shape
+    bf16, colstats: (2 H,) f64 accumulators or None.
+
+    sep (taps 1 only) = (ws, bias, z): the sep conv on x_R inside the launch -- ws: its (64, H) bf16 operand copy
+    [out][in] (not packed), bias: (64,) f32, z: (N, 64) f32 (may be the first N rows of a longer tensor).
+
+    head: the conv that makes x_0 inside the launch; a0 / x0 are then outputs (either may be None: not stored).
+    taps 3: (zq, w, bias) -- zq: (N, 64) bf16, w: the (H, 64) bf16 operand copy [out][in], bias: (H,) f32 (the
+    decoder's 1x1 conv); taps 1: (x, w, bias, patches, P) -- x: the (B, L, C) f32 windows, w: the (H, 32) bf16 operand
+    copy, patches: (N, 32) bf16 output or None, P <= 32 the patch size (patchify + the patch embed)."""
+    N, H = a[-1].shape
     R = len(w1)
     if not (1 <= R <= RES_CHAIN_MAX) or not all(len(v) == R for v in (w2, b1, b2, dh, a1, dx, a)):
         raise nat.NativeError("res_chain_fwd: need R (1..16) entries in every per-block list")
@@ -358,6 +381,49 @@ def res_chain_fwd(a0, x0, w1, w2, b1, b2, dh, a1, dx, a, drop=(0.0, None), seed_
         # the launch's record carries the ConvT it absorbed: its algorithmic flops, and Y and the matrices as bytes
         flops += 2.0 * N * k1 * H * H
         extra = [Y, tb] + list(wt)
+    if sep is not None:
+        ws, sb, z = sep
+        D = 64
+        if taps != 1:
+            raise nat.NativeError("res_chain_fwd: the sep tail needs taps == 1")
+        if ws.dtype != torch.bfloat16 or tuple(ws.shape) != (D, H) or not ws.is_contiguous():
+            raise nat.NativeError(f"res_chain_fwd: sep weights must be a contiguous ({D}, {H}) bfloat16 operand copy")
+        if sb.dtype != torch.float32 or sb.numel() != D or not sb.is_contiguous():
+            raise nat.NativeError(f"res_chain_fwd: sep bias must be ({D},) float32")
+        if z.dtype != torch.float32 or tuple(z.shape) != (N, D) or not z.is_contiguous():
+            raise nat.NativeError(f"res_chain_fwd: sep z must be a contiguous ({N}, {D}) float32 tensor")
+        g.sep_d, g.sep_w, g.sep_bias, g.sep_z = D, ptr(ws), ptr(sb), ptr(z)
+        # the launch's record carries the sep conv it absorbed, as the ConvT tail's does
+        flops += 2.0 * N * D * H
+        extra += [z, sb, ws]
+    if head is not None:
+        hin, hw, hb = head[:3]
+        hk = 64 if taps == 3 else 32
+        if hw.dtype != torch.bfloat16 or tuple(hw.shape) != (H, hk) or not hw.is_contiguous():
+            raise nat.NativeError(f"res_chain_fwd: head weights must be a contiguous ({H}, {hk}) bfloat16 operand copy")
+        if hb.dtype != torch.float32 or hb.numel() != H or not hb.is_contiguous():
+            raise nat.NativeError("res_chain_fwd: head bias must be (H,) float32")
+        if taps == 3:
+            if len(head) != 3 or hin.dtype != torch.bfloat16 or tuple(hin.shape) != (N, hk) or not hin.is_contiguous():
+                raise nat.NativeError(f"res_chain_fwd: the decoder head's input must be a contiguous ({N}, {hk}) "
+                                      "bfloat16 tensor")
+            hp = None
+        else:
+            hp, P = head[3], int(head[4])
+            if hin.dtype != torch.float32 or hin.dim() != 3 or not hin.is_contiguous():
+                raise nat.NativeError("res_chain_fwd: the encoder head's input must be contiguous (B, L, C) float32 windows")
+            Bw, Lw, Cw = hin.shape
+            if not (1 <= P <= hk) or (Lw * Cw) % P or Bw * (Lw * Cw // P) != N:
+                raise nat.NativeError(f"res_chain_fwd: windows {tuple(hin.shape)} do not make {N} patches of {P}")
+            if hp is not None and (hp.dtype != torch.bfloat16 or tuple(hp.shape) != (N, hk) or not hp.is_contiguous()):
+                raise nat.NativeError(f"res_chain_fwd: patches must be a contiguous ({N}, {hk}) bfloat16 tensor")
+            g.head_patches, g.head_L, g.head_C, g.head_P = ptr(hp), Lw, Cw, P
+        g.head_k, g.head_in, g.head_w, g.head_bias = hk, ptr(hin), ptr(hw), ptr(hb)
+        # the launch's record carries the conv it absorbed (the patch embed as its GEMM counted it: P real columns)
+        flops += 2.0 * N * H * (hk if taps == 3 else P)
+        extra += [hin, hw, hb, hp]
+    elif a0 is None or x0 is None:
+        raise nat.NativeError("res_chain_fwd: a0 / x0 missing")
     _maybe_timed(stream, "gemm_bf16", flops,
                  lambda sp: call("aw_res_chain_fwd", ctypes.byref(g), sp),
                  lambda: (f"res_chain_fwd_kernel<{int(taps)}>",

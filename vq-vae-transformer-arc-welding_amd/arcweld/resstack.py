@@ -171,11 +171,12 @@ def _bn_block_bwd(sv, r, gy, w1d, w2d, grads, bns, slot, wgrads, need_copy):
     return gx, gxo
 
 
-def _chain_fwd(sv, weights, biases, RT, save, tail=None):
+def _chain_fwd(sv, weights, biases, RT, save, tail=None, sep=None, head=None):
     """Forward of the whole stack through aw_res_chain_fwd, from sv.xs[0] / sv.a0s[0].  Fills sv with GELU'(h), a1,
     GELU'(x), a per block -- a1 and a as the per-conv route makes them, the saved derivatives in place of its h and x
     (None without `save`) --, the operand copies the backward packs its weights from and the dropout keep bits.
-    tail: see ``forward``; its matrices are packed in the same launch as the stack's."""
+    tail / sep / head: see ``forward``; the tail's matrices are packed in the same launch as the stack's, the sep
+    conv's and the head's operand copies are read as they are."""
     geo = sv.geo
     R, H, taps, T = len(biases), geo.H, geo.taps, sv.T
     x0, a0 = sv.xs[0], sv.a0s[0]
@@ -206,7 +207,7 @@ def _chain_fwd(sv, weights, biases, RT, save, tail=None):
             sv.masks = K.res_dropout_masks_empty(N, R, dev)
     K.res_chain_fwd(a0, x0, pk[0::2], pk[1::2], [b1 for b1, _ in biases], [b2 for _, b2 in biases], sv.hs, sv.a1s,
                     sv.xs[1:], sv.a0s[1:], drop=(sv.p_drop, sv.seeds), seed_ptr=sv.ctr, masks=sv.masks, taps=taps,
-                    seg=geo.S, tail=ktail)
+                    seg=geo.S, tail=ktail, sep=sep, head=head)
 
 
 def _chain_bwd(sv, gx, gxo, grads):
@@ -232,7 +233,7 @@ def _chain_bwd(sv, gx, gxo, grads):
 
 
 def forward(geo, x0, a0, weights, biases, bns=None, *, T, RT, p_drop=0.0, seeds=None, ctr=None, training=False,
-            chain=False, last_operand_only=True, in_place=False, save=True, tail=None):
+            chain=False, last_operand_only=True, in_place=False, save=True, tail=None, sep=None, head=None):
     """R = len(biases) ResBlocks from x0 [N][H] (dtype RT) and a0 = GELU(x0) (operand dtype T).
 
     weights[r]: block r's (conv1, conv2) forward operands [H][Kd]; biases[r]: its (b1, b2); bns: per block the
@@ -244,7 +245,10 @@ def forward(geo, x0, a0, weights, biases, bns=None, *, T, RT, p_drop=0.0, seeds=
     tensor (and the chain stores none of its derivatives).  tail = (Wt [k1 H][H] operand copy, bias (H,) f32,
     Y (N, k1 H) bf16, colstats (2 H,) f64 or None): only on the chain route of a taps = 3 stack -- the chain launch
     also runs the un-patch ConvT on x_R (Y and the BatchNorm column statistics of K.gemm(x_R, Wt, bias_mod=H,
-    stats_mod=H)).
+    stats_mod=H)).  sep = (Ws [64][H] operand copy, bias (64,) f32, z (N, 64) f32): only on the chain route of a
+    taps = 1 stack -- the chain launch also runs the sep conv on x_R (z of K.gemm(x_R, Ws, N, 64, H, bias=bias)).
+    head (chain route only; K.res_chain_fwd's): the launch also runs the conv that makes x_0, and x0 / a0 are outputs
+    the launch fills (what K.gemm(..., C=x0, C2=a0, c2_mode=1) writes).
 
     Returns (x_R or None when only its operand copy was written, the operand copy -- GELU(x_R), or x_R itself under
     last_operand_only --, Saved)."""
@@ -256,8 +260,12 @@ def forward(geo, x0, a0, weights, biases, bns=None, *, T, RT, p_drop=0.0, seeds=
     e = lambda dt: torch.empty(N, H, device=dev, dtype=dt)  # noqa: E731
     if tail is not None and (route != "chain" or geo.taps != 3):
         raise ValueError("resstack.forward: the ConvT tail runs only inside the decoder chain")
+    if sep is not None and (route != "chain" or geo.taps != 1):
+        raise ValueError("resstack.forward: the sep tail runs only inside the encoder chain")
+    if head is not None and route != "chain":
+        raise ValueError("resstack.forward: a head runs only inside a chain launch")
     if route == "chain":
-        _chain_fwd(sv, weights, biases, RT, save, tail)
+        _chain_fwd(sv, weights, biases, RT, save, tail, sep, head)
         return sv.xs[R], sv.a0s[R], sv
     x, a, h, a1 = x0, a0, None, None
     for r in range(R):

@@ -199,25 +199,37 @@ def forward(m, x, training: bool, need_backward: bool, dtype=None, seed: int = 0
     dec_w = [(ops[f"dec{r}_1"], ops[f"dec{r}_2"]) for r in range(R)]
     sv.ops = ops
 
-    # ---- patch embed
+    # ---- patch embed.  With the encoder chain and the reference's patch 25 (32 padded columns) patchify and the GEMM
+    #      run as the head of the chain launch, which writes patches, x0 and a0 itself (ARCWELD_CHAIN_HEAD=0: these
+    #      two launches)
+    enc_chain = K.res_chain_ok(H, R, T, RT) and pr["enc_bn"] is None
+    enc_head = enc_chain and sh.ldp == 32 and K.chain_head_ok()
     patches = e(N, sh.ldp, dt=T)
-    K.patchify(x, P, patches)
     x0, a0 = e(N, H, dt=RT), e(N, H, dt=T)
-    K.gemm(patches, Wp, N, H, sh.ldp, bias=pr["pe"].bias, C=x0, C2=a0, c2_mode=1, flops=2 * N * H * P)
+    if not enc_head:
+        K.patchify(x, P, patches)
+        K.gemm(patches, Wp, N, H, sh.ldp, bias=pr["pe"].bias, C=x0, C2=a0, c2_mode=1, flops=2 * N * H * P)
 
     # ---- encoder ResBlocks (per-token: centre taps).  bf16: the whole stack as ONE persistent launch
     #      (csrc/reschain.hip), the same tensors bit for bit; the last block writes only the operand copy of x_R (all
     #      the sep conv consumes)
     stack = dict(T=T, RT=RT, p_drop=p_drop, ctr=sv.ctr, training=training, save=need_backward)
+    # The sep conv (D = 64) rides as the tail of the encoder chain launch when that runs: x_R is still in LDS there,
+    # so z costs 16 more K steps on a quarter of the fragments and no launch of its own (ARCWELD_SEP_TAIL=0: the GEMM
+    # below)
+    z = e(N, D)
+    sep_tail = enc_chain and D == 64 and K.sep_tail_ok()
     _, xR_T, sv.enc = resstack.forward(resstack.Geometry(1, H, S), x0, a0, enc_w, _biases(pr["enc"]), pr["enc_bn"],
                                        seeds=[_mix(seed, 100 + r) for r in range(R)],
-                                       chain=K.res_chain_ok(H, R, T, RT), **stack)
+                                       chain=enc_chain,
+                                       sep=(Ws, pr["sep"].bias, z) if sep_tail else None,
+                                       head=(x, Wp, pr["pe"].bias, patches, P) if enc_head else None, **stack)
     if R == 0:
         xR_T = _operand(x0, T)
 
     # ---- SepCNNBlock -> z (B, S, D)
-    z = e(N, D)
-    K.gemm(xR_T, Ws, N, D, H, bias=pr["sep"].bias, C=z)
+    if not sep_tail:
+        K.gemm(xR_T, Ws, N, D, H, bias=pr["sep"].bias, C=z)
 
     # ---- vector quantizer
     Kc = sh.K
@@ -242,7 +254,6 @@ def forward(m, x, training: bool, need_backward: bool, dtype=None, seed: int = 0
 
     # ---- decoder: 1x1 conv + ResBlocks with k=3 convs along the window
     y0, ya0 = e(N, H, dt=RT), e(N, H, dt=T)
-    K.gemm(zq_T, Wd0, N, H, D, bias=pr["dec0"].bias, C=y0, C2=ya0, c2_mode=1)
     # In the bf16 operand mode the ConvT output Y is bf16 (what autocast keeps for a ConvTranspose1d output; the BN
     # statistics still come from the f32 values in the epilogue): half the bytes of the GEMM's output and of the head's
     # passes over Y.  Round 3 measured it even over the step (the head passes are VALU-bound); on the round-4 step it
@@ -255,9 +266,15 @@ def forward(m, x, training: bool, need_backward: bool, dtype=None, seed: int = 0
     # LDS there, so the ConvT is k1 more 1-tap convs and no launch of its own (ARCWELD_CONVT_TAIL=0: the GEMM below)
     dec_chain = K.res_chain_ok(H, R, T, RT, 3, S, "DEC") and pr["dec_bn"] is None
     convt_tail = dec_chain and bf_y and k1 <= nat.RES_TAIL_MAX and K.convt_tail_ok()
+    # ... and the 1x1 conv (D = 64) as its head: the launch loads its rows of zq_T and writes y0 / ya0 itself
+    # (ARCWELD_CHAIN_HEAD=0: the GEMM below)
+    dec_head = dec_chain and D == 64 and K.chain_head_ok()
+    if not dec_head:
+        K.gemm(zq_T, Wd0, N, H, D, bias=pr["dec0"].bias, C=y0, C2=ya0, c2_mode=1)
     _, yR_T, sv.dec = resstack.forward(resstack.Geometry(3, H, S), y0, ya0, dec_w, _biases(pr["dec"]), pr["dec_bn"],
                                        seeds=[_mix(seed, 200 + r) for r in range(R)], chain=dec_chain,
-                                       tail=(Wt1, pr["t1"].bias, Y, colstats) if convt_tail else None, **stack)
+                                       tail=(Wt1, pr["t1"].bias, Y, colstats) if convt_tail else None,
+                                       head=(zq_T, Wd0, pr["dec0"].bias) if dec_head else None, **stack)
     if R == 0:
         yR_T = _operand(y0, T)
 

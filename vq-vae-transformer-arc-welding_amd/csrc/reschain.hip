@@ -45,7 +45,10 @@
 //  * the decoder's forward chain may go on past the last block (TAIL): the un-patch ConvTranspose1d(H -> H, k1) that
 //    consumes x_R is k1 independent 1-tap convs over the image x_R was just staged in, so it runs there, with its
 //    bias, bf16 output Y [N][k1 H] and BatchNorm column statistics, instead of as a GEMM launch of its own
-//    (model/vq_vae_patch_embedd.py reverse_patch_embed.proj[0]).
+//    (model/vq_vae_patch_embedd.py reverse_patch_embed.proj[0]).  The encoder's goes on with
+//    the sep conv (H -> 64) the same way, and either forward chain may begin with the conv that makes its x_0 (HEAD):
+//    the decoder's 1x1 conv on the quantized rows, patchify + the patch embed on the raw windows -- a conv of one or
+//    two K steps whose epilogue fills the residual registers and conv 0's operand image, in place of loading both.
 // Per element the epilogues run the unfused GEMM epilogue's operations in its order (gemm_core.h), and each
 // accumulator sees the same MFMA sequence (K ascending in 32-deep steps, tap-major as the implicit conv GEMM), so
 // the forward's outputs a1 / a / keep bits are the unfused path's bit for bit; the saved derivatives are GELU' of the
@@ -159,8 +162,17 @@ template <class G> __device__ __forceinline__ int ec_off(int tok, int chunk) {
   return G::R0 + (tok >> 4) * G::JS + (tok & 15) * EC_ROWB + ((chunk ^ G::key(tok & 15)) << 4);
 }
 
+// the decoder images' zero rows: cleared once, never written again
+template <class G> __device__ __forceinline__ void ec_zero_rows(char* img, int tid) {
+  if constexpr (G::R0 != 0) {
+    for (int c = tid; c < 2 * 5 * 64; c += EC_NTH) {   // 2 images x 5 zero rows x 64 chunks
+      const int im = c / 320, row = (c % 320) >> 6, ch = c & 63;
+      *reinterpret_cast<uint4*>(img + im * G::IMG + row * G::JS + ch * 16) = uint4{0u, 0u, 0u, 0u};
+    }
+  }
+}
 // The first operand image of a chain: rows [row0, row0 + 64) of a [N][H] bf16 tensor (zeros past N); the decoder
-// images' zero rows are cleared here and never written again.
+// images' zero rows are cleared here.
 template <class G>
 __device__ __forceinline__ void ec_load_image(char* img, const void* src, int64_t row0, uint32_t nbytes, int tid) {
   const rsrc_t rs = ec_rsrc(src, nbytes);
@@ -173,12 +185,7 @@ __device__ __forceinline__ void ec_load_image(char* img, const void* src, int64_
     memcpy(&u, &v, 16);
     *reinterpret_cast<uint4*>(img + ec_off<G>(tok, ch)) = u;
   }
-  if constexpr (G::R0 != 0) {
-    for (int c = tid; c < 2 * 5 * 64; c += EC_NTH) {   // 2 images x 5 zero rows x 64 chunks
-      const int im = c / 320, row = (c % 320) >> 6, ch = c & 63;
-      *reinterpret_cast<uint4*>(img + im * G::IMG + row * G::JS + ch * 16) = uint4{0u, 0u, 0u, 0u};
-    }
-  }
+  ec_zero_rows<G>(img, tid);
 }
 
 // ---------------------------------------------------------------- inter-wave hand-off through LDS
@@ -429,12 +436,17 @@ template <class G> __device__ __forceinline__ void ec_init(char* smem, int tid) 
   if (tid < 8) *ec_flag<G>(smem, tid) = 0;
 }
 
-// TAIL (TAPS = 3): the un-patch ConvT as tail_k1 more convs over the last image (see the end of the kernel)
-template <int TAPS, bool DROP, bool WT, bool TAIL>
+// TAIL: the conv that consumes x_R, run over the last image (see the end of the kernel).  TAPS = 3: the un-patch
+// ConvT as tail_k1 more convs; TAPS = 1: the sep conv (H -> 64) as one 64-channel conv.
+// HEAD: the conv that makes x_0 runs in the launch too (see the prologue).  TAPS = 3: the decoder's 1x1 conv
+// (64 -> H) on the quantized rows; TAPS = 1: patchify + the patch embed (32 -> H) on the raw windows.
+template <int TAPS, bool DROP, bool WT, bool TAIL, bool HEAD>
 __global__ __launch_bounds__(EC_NTH) void res_chain_fwd_kernel(aw_res_chain_fwd_args P) {
   using G = EcGeo<TAPS>;
-  static_assert(!TAIL || TAPS == 3, "the ConvT tail follows the decoder chain");
-  __shared__ __attribute__((aligned(16))) char smem[TAIL ? G::LDS_TAIL : G::LDS];
+  constexpr bool SEP = TAIL && TAPS == 1;     // the encoder's tail
+  constexpr bool CT = TAIL && TAPS == 3;      // the decoder's
+  constexpr int HK = TAPS == 1 ? 32 : 64;     // the head's K: bf16 elements per operand row
+  __shared__ __attribute__((aligned(16))) char smem[CT ? G::LDS_TAIL : G::LDS];
   const int tid = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.x * EC_ROWS;
   const EcLane<G, 1> L(tid);
@@ -442,17 +454,61 @@ __global__ __launch_bounds__(EC_NTH) void res_chain_fwd_kernel(aw_res_chain_fwd_
   const int R = P.R, NC = 2 * R;
 
   ec_init<G>(smem, tid);
-  if constexpr (TAIL) *reinterpret_cast<float*>(smem + G::TBIAS + 4 * tid) = P.tail_bias[tid];
-  ec_load_image<G>(smem, P.a0, row0, nbytes, tid);
+  if constexpr (CT) *reinterpret_cast<float*>(smem + G::TBIAS + 4 * tid) = P.tail_bias[tid];
   u32x2 xr[4][4];   // the residual stream x (bf16) of this lane's fragments, kept in registers through the chain
-  ec_load_frags(xr, ec_rsrc(P.x0, nbytes), ec_frag_off(row0, L.li, L.w, L.g));
   uint4 wf[2][4];
-  {
+  if constexpr (!HEAD) {
+    ec_load_image<G>(smem, P.a0, row0, nbytes, tid);
+    ec_load_frags(xr, ec_rsrc(P.x0, nbytes), ec_frag_off(row0, L.li, L.w, L.g));
     const rsrc_t r0 = ec_rsrc(P.w1[0], G::WBYTES);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       wf[0][i] = ec_wload(r0, L.wl, ec_woff<G>(i, 0));
       wf[1][i] = ec_wload(r0, L.wl, ec_woff<G>(i, 1));
+    }
+  } else {
+    // The head's operand rows (64 tokens x HK bf16: chunks 0 .. HK / 8 - 1 of each row) go into image 1, the spare
+    // one -- conv 0 reads image 0, which the head's epilogue writes.  8 threads per token.
+    ec_zero_rows<G>(smem, tid);
+    const int tok = tid >> 3, pc = tid & 7;
+    if constexpr (TAPS == 3) {
+      // rows of zq_T [N][64] bf16, zeros past N: one 16-B chunk per thread
+      const auto v = __builtin_amdgcn_raw_buffer_load_b128(ec_rsrc(P.head_in, (uint32_t)(P.N * HK * 2)),
+                                                           (uint32_t)((row0 + tok) * HK * 2 + pc * 16), 0, 0);
+      uint4 u;
+      memcpy(&u, &v, 16);
+      *reinterpret_cast<uint4*>(smem + G::IMG + ec_off<G>(tok, pc)) = u;
+    } else {
+      // patchify (aw_patchify): element j of token t of a window is its channel-major flat element f = t P + j,
+      // c = f / L, l = f % L, of x [B][L][C] f32; elements P .. 31 are zero.  4 elements per thread, also stored as
+      // the bf16 patches rows (the patch-embed weight gradient reads them)
+      const int Lw = P.head_L, C = P.head_C, Pp = P.head_P, S = Lw * C / Pp;
+      const int64_t row = row0 + tok, b = row / S;
+      const int t = (int)(row - b * S);
+      const float* xw = reinterpret_cast<const float*>(P.head_in) + b * Lw * C;
+      float v[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int j = 4 * pc + e, f = t * Pp + j, c = f / Lw, l = f - c * Lw;
+        v[e] = row < P.N && j < Pp ? xw[l * C + c] : 0.f;
+      }
+      const u32x2 u = ec_pack(v);
+      ec_lds_w8(smem, G::IMG + ec_off<G>(tok, pc >> 1) + (pc & 1) * 8, u);
+      ec_store8(ec_rsrc(P.head_patches, (uint32_t)(P.N * HK * 2)), (uint32_t)(row * HK * 2 + pc * 8), u);
+    }
+    // the head's bias in the wave's slot (conv 0 parks its own there at the end of its K loop)
+    *reinterpret_cast<float*>(smem + G::BIAS + 4 * tid) = P.head_bias[tid];
+    // the head's weights straight from the [H][HK] operand copy: a fragment is 16 rows x 16 B per lane
+    const rsrc_t rh = ec_rsrc(P.head_w, EC_H * HK * 2);
+    const int ho = (64 * L.w + L.li) * HK * 2 + 16 * L.g;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int s = 0; s < HK / 32; ++s) wf[s][i] = ec_wload(rh, ho, i * 16 * HK * 2 + 64 * s);
+    if constexpr (HK == 32) {   // one head step: conv 0's step 1 is due in wf[1] already
+      const rsrc_t r0 = ec_rsrc(P.w1[0], G::WBYTES);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) wf[1][i] = ec_wload(r0, L.wl, ec_woff<G>(i, 1));
     }
   }
   const rsrc_t rmask = ec_rsrc(DROP ? P.drop_masks : nullptr, (uint32_t)(R * gridDim.x * EC_NTH * 8));
@@ -462,13 +518,69 @@ __global__ __launch_bounds__(EC_NTH) void res_chain_fwd_kernel(aw_res_chain_fwd_
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __syncthreads();
 
+  if constexpr (HEAD) {
+    // The head conv: HK / 32 K steps over the centre-tap rows of image 1, the work split of every other conv (wave w:
+    // channels 64w .. 64w + 63, 4 x 4 fragments, K ascending -- aw_gemm's MFMA sequence), and the weight stream runs
+    // on into conv 0's first two steps.  Epilogue per fragment: v = acc + bias; the residual registers get bf16(v)
+    // (what loading the stored x_0 gave), GELU(v) goes into image 0 as conv 0's operand (aw_gelu4: aw_gemm's
+    // c2_mode 1), and x_0 / a_0 are stored as whole lines (scratch / own slice; either may be NULL).  Hand-off to
+    // conv 0: one workgroup barrier -- the waves left the prologue's barrier one or two K steps ago and have not
+    // drifted apart yet, so it costs what that barrier costs, and every slice count of the convs stays as it is.
+    constexpr int TC = G::KS / 32;   // the centre tap
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const rsrc_t r0 = ec_rsrc(P.w1[0], G::WBYTES);
+    const int rbi = L.rb[TC] + G::IMG;
+#pragma unroll
+    for (int s = 0; s < HK / 32; ++s) {
+      uint4 bf[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bf[j] = ec_lds_r16(smem, (rbi ^ (64 * s)) + j * G::JS);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[s][i]),
+                                                              __builtin_bit_cast(bf16x8, bf[j]), acc[i][j], 0, 0, 0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) wf[s][i] = ec_wload(r0, L.wl, ec_woff<G>(i, s));
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    const EcStore<G> S(tid, row0);
+    const rsrc_t rx = ec_rsrc(P.x0, nbytes);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float4 b4 = *reinterpret_cast<const float4*>(smem + G::BIAS + 256 * L.w + 64 * i + 16 * L.g);
+        const float bv[4] = {b4.x, b4.y, b4.z, b4.w};
+        float v[4], y[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = acc[i][j][e] + bv[e];
+        xr[i][j] = ec_pack(v);
+        aw_gelu4(v, y);
+        ec_lds_w8(smem, L.wb(i) + G::JS * j, ec_pack(y));
+        ec_lds_w8(smem, S.sw[i], xr[i][j]);
+        ec_frag_fence(4 * j + i);
+      }
+      ec_store_scratch<G, WT>(smem, j, S, rx);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __syncthreads();
+    ec_store_slice<G, WT>(smem, 0, S, ec_rsrc(P.a0, nbytes));
+  }
+
   for (int c = 0; c < NC; ++c) {
     const int r = c >> 1;
     const bool second = (c & 1) != 0;
     const rsrc_t rc = ec_rsrc(second ? P.w2[r] : P.w1[r], G::WBYTES);
     // with a tail the weight stream runs on into its first matrix, which is packed as a 1-tap matrix
-    const bool tail_next = TAIL && c + 1 == NC;
-    const bool has_next = TAIL || c + 1 < NC;
+    const bool tail_next = CT && c + 1 == NC;
+    const bool has_next = CT || c + 1 < NC;
     const rsrc_t rn = ec_rsrc(tail_next ? P.tail_w[0] : has_next ? (second ? P.w1[r + 1] : P.w2[r]) : nullptr,
                               tail_next ? EcGeo<1>::WBYTES : G::WBYTES);
     const int io = (c & 1) * G::IMG, no = ((c + 1) & 1) * G::IMG;
@@ -487,7 +599,7 @@ __global__ __launch_bounds__(EC_NTH) void res_chain_fwd_kernel(aw_res_chain_fwd_
       *reinterpret_cast<float*>(smem + G::BIAS + 256 * L.w + 4 * L.lane) = bias_l;
       if (DROP && second) ec_store8(rmask, (uint32_t)(ec_keep_idx(r, tid) * 8), u32x2{kb[0], kb[1]});
     };
-    if constexpr (TAIL)
+    if constexpr (CT)
       ec_conv_g<G, G::KS, false>(acc, wf, smem, L.rb, io, rc, rn, true, L.wl,
                                  tail_next ? L.w * EcGeo<1>::WWAVE + L.lane * 16 : L.wl, tail_next ? 16 : G::KS, L.w, c,
                                  park, hash);
@@ -575,7 +687,7 @@ __global__ __launch_bounds__(EC_NTH) void res_chain_fwd_kernel(aw_res_chain_fwd_
     }
   }
 
-  if constexpr (TAIL) {
+  if constexpr (CT) {
     // The un-patch ConvT: tail_k1 independent 1-tap convs over the x_R image (image 0: NC is even), each the centre
     // tap walk of that image with a 1-tap packed matrix.  Only the first waits for the other waves' slices.  Epilogue
     // per fragment: v = acc + bias, column sums of v and v * v (f32, before the rounding, real rows only), bf16 into
@@ -655,6 +767,43 @@ __global__ __launch_bounds__(EC_NTH) void res_chain_fwd_kernel(aw_res_chain_fwd_
       const double a = red[L.lane], b = red[64 + L.lane];
       atomicAdd(P.tail_colstats + 64 * L.w + L.lane, a);
       atomicAdd(P.tail_colstats + EC_H + 64 * L.w + L.lane, b);
+    }
+  }
+
+  if constexpr (SEP) {
+    // The sep conv (H -> 64 channels, one tap per token) over the x_R image (image 0: NC is even): 4 channel blocks x 4
+    // token groups of fragments, two per wave -- wave w: channel block i = w & 3, token groups 2 (w >> 2) and + 1 --,
+    // each accumulator over the 16 K steps ascending, as aw_gemm runs them.  The weights come straight from the
+    // [64][H] operand copy: a fragment is 16 rows x 64 B, 16 loads per lane in all, issued ahead of the waits for the
+    // other waves' slices (x_R and the residual registers are dead here, so they cost no spill).  z = acc + bias in
+    // f32, 16 B per lane from the accumulator layout; rows at or past N fall outside z's descriptor.
+    const int i = L.w & 3, j0 = 2 * (L.w >> 2);
+    const rsrc_t rw = ec_rsrc(P.sep_w, 64 * EC_ROWB);
+    const int wo = (16 * i + L.li) * EC_ROWB + 16 * L.g;
+    uint4 ws[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) ws[s] = ec_wload(rw, wo, 64 * s);
+    float bv[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) bv[e] = P.sep_bias[16 * i + 4 * L.g + e];
+    f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      if ((s & 1) == 0 && (s >> 1) != L.w) ec_wait<G>(smem, s >> 1, NC);
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj) {
+        const uint4 bf = ec_lds_r16(smem, (L.rb[0] ^ (64 * (s & 3))) + (s >> 2) * 256 + (j0 + jj) * G::JS);
+        acc[jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ws[s]),
+                                                          __builtin_bit_cast(bf16x8, bf), acc[jj], 0, 0, 0);
+      }
+    }
+    const rsrc_t rz = ec_rsrc(P.sep_z, (uint32_t)(P.N * 64 * 4));
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) {
+      uint4 v;
+      v.x = __float_as_uint(acc[jj][0] + bv[0]), v.y = __float_as_uint(acc[jj][1] + bv[1]);
+      v.z = __float_as_uint(acc[jj][2] + bv[2]), v.w = __float_as_uint(acc[jj][3] + bv[3]);
+      ec_store16<WT>(rz, (uint32_t)(((row0 + 16 * (j0 + jj) + L.li) * 64 + 16 * i + 4 * L.g) * 4), 0, v);
     }
   }
 }
@@ -893,12 +1042,12 @@ __global__ __launch_bounds__(EC_NTH) void res_mask_kernel(MaskSeeds S, const uin
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-template <int TAPS, bool TAIL>
+template <int TAPS, bool TAIL, bool HEAD>
 void launch_fwd(const aw_res_chain_fwd_args* a, bool drop, bool wt, dim3 grid, hipStream_t s) {
-  if (drop && wt) hipLaunchKernelGGL((res_chain_fwd_kernel<TAPS, true, true, TAIL>), grid, dim3(EC_NTH), 0, s, *a);
-  else if (drop) hipLaunchKernelGGL((res_chain_fwd_kernel<TAPS, true, false, TAIL>), grid, dim3(EC_NTH), 0, s, *a);
-  else if (wt) hipLaunchKernelGGL((res_chain_fwd_kernel<TAPS, false, true, TAIL>), grid, dim3(EC_NTH), 0, s, *a);
-  else hipLaunchKernelGGL((res_chain_fwd_kernel<TAPS, false, false, TAIL>), grid, dim3(EC_NTH), 0, s, *a);
+  if (drop && wt) hipLaunchKernelGGL((res_chain_fwd_kernel<TAPS, true, true, TAIL, HEAD>), grid, dim3(EC_NTH), 0, s, *a);
+  else if (drop) hipLaunchKernelGGL((res_chain_fwd_kernel<TAPS, true, false, TAIL, HEAD>), grid, dim3(EC_NTH), 0, s, *a);
+  else if (wt) hipLaunchKernelGGL((res_chain_fwd_kernel<TAPS, false, true, TAIL, HEAD>), grid, dim3(EC_NTH), 0, s, *a);
+  else hipLaunchKernelGGL((res_chain_fwd_kernel<TAPS, false, false, TAIL, HEAD>), grid, dim3(EC_NTH), 0, s, *a);
 }
 template <int TAPS>
 void launch_bwd(const aw_res_chain_bwd_args* a, bool drop, bool wt, dim3 grid, hipStream_t s) {
@@ -922,7 +1071,28 @@ void launch_bwd(const aw_res_chain_bwd_args* a, bool drop, bool wt, dim3 grid, h
 
 extern "C" int aw_res_chain_fwd(const aw_res_chain_fwd_args* a, void* stream) {
   CHAIN_SHAPE_CHECKS("aw_res_chain_fwd");
-  AW_REQUIRE(a->a0 && a->x0 && aligned16(a->a0) && aligned16(a->x0), "aw_res_chain_fwd: a0 / x0 missing or unaligned");
+  if (a->head_k == 0) {
+    AW_REQUIRE(!a->head_in && !a->head_w && !a->head_bias && !a->head_patches && !a->head_L && !a->head_C && !a->head_P,
+               "aw_res_chain_fwd: head fields without head_k");
+    AW_REQUIRE(a->a0 && a->x0, "aw_res_chain_fwd: a0 / x0 missing");
+  } else {
+    AW_REQUIRE(a->head_k == (a->taps == 3 ? 64 : 32), "aw_res_chain_fwd: head_k must be 64 (taps 3) or 32 (taps 1), got %d",
+               a->head_k);
+    AW_REQUIRE(a->head_in && a->head_w && a->head_bias && aligned16(a->head_w) &&
+                   ((uintptr_t)a->head_in & (a->taps == 3 ? 15 : 3)) == 0,
+               "aw_res_chain_fwd: head_in / head_w / head_bias missing or unaligned");
+    if (a->taps == 3) {
+      AW_REQUIRE(!a->head_patches && !a->head_L && !a->head_C && !a->head_P,
+                 "aw_res_chain_fwd: the decoder head takes no window geometry");
+    } else {
+      AW_REQUIRE(a->head_L >= 1 && a->head_C >= 1 && a->head_P >= 1 && a->head_P <= 32 &&
+                     (int64_t)a->head_L * a->head_C % a->head_P == 0 &&
+                     a->N % ((int64_t)a->head_L * a->head_C / a->head_P) == 0 && ((uintptr_t)a->head_patches & 7) == 0,
+                 "aw_res_chain_fwd: the encoder head needs windows of L x C elements in whole patches of P <= 32 and "
+                 "N a multiple of the tokens per window (L %d, C %d, P %d)", a->head_L, a->head_C, a->head_P);
+    }
+  }
+  AW_REQUIRE(aligned16(a->a0) && aligned16(a->x0), "aw_res_chain_fwd: a0 / x0 unaligned");
   for (int r = 0; r < a->R; ++r) {
     AW_REQUIRE(a->w1[r] && a->w2[r] && a->b1[r] && a->b2[r] && aligned16(a->w1[r]) && aligned16(a->w2[r]) &&
                aligned16(a->b1[r]) && aligned16(a->b2[r]), "aw_res_chain_fwd: block %d weights missing or unaligned", r);
@@ -945,9 +1115,22 @@ extern "C" int aw_res_chain_fwd(const aw_res_chain_fwd_args* a, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)((a->N + EC_ROWS - 1) / EC_ROWS));
   const bool drop = a->drop_p > 0.f, wt = a->store_policy == AW_STORE_WT;
-  if (a->tail_k1) launch_fwd<3, true>(a, drop, wt, grid, s);
-  else if (a->taps == 3) launch_fwd<3, false>(a, drop, wt, grid, s);
-  else launch_fwd<1, false>(a, drop, wt, grid, s);
+  if (a->sep_d == 0) {
+    AW_REQUIRE(!a->sep_w && !a->sep_bias && !a->sep_z, "aw_res_chain_fwd: sep fields without sep_d");
+  } else {
+    AW_REQUIRE(a->taps == 1 && a->sep_d == 64, "aw_res_chain_fwd: the sep tail needs taps == 1 and sep_d == 64 (got %d)",
+               a->sep_d);
+    AW_REQUIRE(a->sep_w && aligned16(a->sep_w) && a->sep_bias && a->sep_z && aligned16(a->sep_z),
+               "aw_res_chain_fwd: sep_w / sep_bias / sep_z missing or unaligned");
+  }
+  const bool head = a->head_k != 0;
+  if (a->taps == 3) {
+    if (a->tail_k1) head ? launch_fwd<3, true, true>(a, drop, wt, grid, s) : launch_fwd<3, true, false>(a, drop, wt, grid, s);
+    else head ? launch_fwd<3, false, true>(a, drop, wt, grid, s) : launch_fwd<3, false, false>(a, drop, wt, grid, s);
+  } else {
+    if (a->sep_d) head ? launch_fwd<1, true, true>(a, drop, wt, grid, s) : launch_fwd<1, true, false>(a, drop, wt, grid, s);
+    else head ? launch_fwd<1, false, true>(a, drop, wt, grid, s) : launch_fwd<1, false, false>(a, drop, wt, grid, s);
+  }
   return aw::check_launch("aw_res_chain_fwd");
 }
 
