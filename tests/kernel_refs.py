@@ -1,4 +1,5 @@
-"""fp64 restatements of the small HIP kernels (csrc/bn.hip, csrc/transformer.hip), shared by the direct kernel tests.
+"""fp64 restatements of the small HIP kernels (csrc/bn.hip, csrc/transformer.hip) and of the causal-attention training
+kernels (csrc/attention.hip and the VALU kernels of csrc/transformer.hip), shared by the direct kernel tests.
 
 Everything here is plain torch/numpy in double precision, evaluated on the inputs the kernels saw (already rounded to
 their storage type).  tests/test_kernel_refs_cpu.py checks these helpers against torch's own modules without a GPU, so
@@ -140,6 +141,159 @@ def attn_cached_ref(q_new, k_all, v_all, pos0):
     i = torch.arange(n_new, device=q_new.device)[:, None]
     att = att.masked_fill(j > pos0 + i, float("-inf")).softmax(-1)
     return torch.einsum("bhij,bjhe->bihe", att, v_all).reshape(B, n_new, nh * hs)
+
+
+# ------------------------------------------------------------------------------------------ causal attention, training
+LOG2E = 1.4426950408889634
+ATTN_RESCALE_STEP = 8.0 / LOG2E      # growth of a row's running max (scaled score) that makes the MFMA forward rescale
+
+
+def _bf16(x):
+    return x.to(torch.bfloat16).to(torch.float64)
+
+
+def _same(x):
+    return x
+
+
+def _attn_heads(x, B, T, nh, hs):
+    """(B*T, nh*hs) -> (B, nh, T, hs) double."""
+    return x.double().reshape(B, T, nh, hs).transpose(1, 2)
+
+
+def _attn_rows(x, B, T, nh, hs):
+    """(B, nh, T, hs) -> (B*T, nh*hs)."""
+    return x.transpose(1, 2).reshape(B * T, nh * hs)
+
+
+def _attn_scores(qkv, B, T, nh, d):
+    """q, k, v (B, nh, T, hs) double and the masked scaled scores (B, nh, T, T)."""
+    hs = d // nh
+    q, k, v = (_attn_heads(t, B, T, nh, hs) for t in qkv.view(B * T, 3, d).unbind(1))
+    s = (q @ k.transpose(-2, -1)) / math.sqrt(hs)
+    causal = torch.ones(T, T, dtype=torch.bool, device=qkv.device).tril()
+    return q, k, v, s.masked_fill(~causal, float("-inf"))
+
+
+def _attn_train(qkv, dy, B, T, nh, d, keep, p, rnd_p, rnd_y, rnd_ds, rnd_out):
+    """Forward and backward of causal attention written out in double precision; the four ``rnd_*`` callables are the
+    identity (attn_train_ref) or a bf16 rounding (attn_bf16_model) at the places named there."""
+    hs = d // nh
+    scale = 1.0 / math.sqrt(hs)
+    q, k, v, s = _attn_scores(qkv, B, T, nh, d)
+    g = _attn_heads(dy, B, T, nh, hs)
+    lse = torch.logsumexp(s, dim=-1)
+    P = (s - lse[..., None]).exp()                       # softmax; exactly 0 above the diagonal
+    ms = None if keep is None else keep.to(device=qkv.device, dtype=torch.float64) / (1.0 - p)
+    Pv = rnd_p(P if ms is None else P * ms)              # the (dropped) probabilities as P.V and P^T.dO take them
+    y = rnd_y(Pv @ v)                                    # y as stored: delta is taken from the stored y
+    delta = (g * y).sum(-1)
+    dP = g @ v.transpose(-2, -1)
+    if ms is not None:
+        dP = dP * ms
+    dS = rnd_ds(P * (dP - delta[..., None]))
+    dq = rnd_out((dS @ k) * scale)
+    dk = rnd_out((dS.transpose(-2, -1) @ q) * scale)
+    dv = rnd_out(Pv.transpose(-2, -1) @ g)
+    dqkv = torch.cat([_attn_rows(t, B, T, nh, hs) for t in (dq, dk, dv)], dim=1)
+    return _attn_rows(y, B, T, nh, hs), lse.reshape(-1), dqkv, delta.reshape(-1)
+
+
+def attn_train_ref(qkv, dy, B, T, nh, d, keep=None, p=0.0):
+    """Causal self-attention (model/transformer_block.py:37-63) and its input gradients in double precision on the
+    inputs as the kernels saw them: qkv (B*T, 3d), dy (B*T, d) -> y (B*T, d), lse (B*nh*T,), dqkv (B*T, 3d) and
+    delta = rowsum(dy . y) (B*nh*T,).  ``keep`` (B, nh, T, T) bool with ``p``: attention-probability dropout, the
+    mask applied after the softmax with the 1 / (1 - p) scaling (lse is that of the undropped row).  The backward
+    formulas are written out (P, dP, dS), no autograd."""
+    return _attn_train(qkv, dy, B, T, nh, d, keep, p, _same, _same, _same, _same)
+
+
+def attn_bf16_model(qkv, dy, B, T, nh, d, keep=None, p=0.0, round_p=True, round_y=True, round_ds=True,
+                    round_out=True):
+    """attn_train_ref with a bf16 rounding at exactly the places the MFMA kernels (csrc/attention.hip) round: P
+    before P.V and before P^T.dO, y before delta = dO.y (the stored y), dS before dS.K and dS^T.Q, and the four
+    outputs.  Everything else stays fp64, so its distance from attn_train_ref is the error a correct bf16 kernel
+    cannot avoid.  The VALU kernels (csrc/transformer.hip) keep P and dS in f32: round_p = round_ds = False is
+    their model.  All four switches off gives attn_train_ref bit for bit."""
+    rnd = [_bf16 if on else _same for on in (round_p, round_y, round_ds, round_out)]
+    return _attn_train(qkv, dy, B, T, nh, d, keep, p, *rnd)
+
+
+ATTN_REGIMES = ("flat", "big", "spike", "ramp")
+
+
+def attn_regime(name, B, nh, T, hs, dtype, seed):
+    """qkv (B*T, 3*nh*hs) and dy (B*T, nh*hs) of ``dtype`` on the CPU from a seeded generator (e0 = first head
+    dimension, j = position):
+      flat   randn (the control: scaled logits ~ N(0, 1))
+      big    q and k x 3
+      spike  q x 1.5 and every key at j = 40 (mod 64) x 6
+      ramp   k = 0.5 randn + 0.25 j e0, q = 0.5 randn + 0.4 sqrt(hs) e0: the scaled score rises by 0.1 per key."""
+    g = torch.Generator().manual_seed(seed)
+    q, k, v, dy = (torch.randn(B, nh, T, hs, generator=g, dtype=torch.float64) for _ in range(4))
+    e0 = torch.zeros(hs, dtype=torch.float64)
+    e0[0] = 1.0
+    if name == "big":
+        q, k = q * 3, k * 3
+    elif name == "spike":
+        q = q * 1.5
+        k = k.clone()
+        k[..., 40::64, :] *= 6
+    elif name == "ramp":
+        k = k * 0.5 + 0.25 * torch.arange(T, dtype=torch.float64)[:, None] * e0
+        q = q * 0.5 + 0.4 * math.sqrt(hs) * e0
+    elif name != "flat":
+        raise ValueError(name)
+    qkv = torch.cat([_attn_rows(t, B, T, nh, hs) for t in (q, k, v)], dim=1)
+    return qkv.to(dtype).contiguous(), _attn_rows(dy, B, T, nh, hs).to(dtype).contiguous()
+
+
+def attn_rescale_events(qkv, B, T, nh, d, tile, step=ATTN_RESCALE_STEP):
+    """(rescale, stale) summed over all rows: the key tiles after a row's first where its running max of the scaled
+    score grows by more than ``step``, and those where it grows by an amount in (0, step].  At the default step and
+    tile 64 ``rescale`` counts the firings of the MFMA forward's lazy rescale and ``stale`` the tiles it processes
+    with a stale max; the VALU kernels (tile 32) rescale on every tile, by exp(-growth)."""
+    _, _, _, s = _attn_scores(qkv, B, T, nh, d)
+    tmax = torch.stack([s[..., t0:t0 + tile].max(-1).values for t0 in range(0, T, tile)], dim=-1)
+    run = torch.cummax(tmax, dim=-1).values              # tile 0 holds key 0: finite for every row
+    grow = run[..., 1:] - run[..., :-1]
+    return int((grow > step).sum()), int(((grow > 0) & (grow <= step)).sum())
+
+
+def attn_keep(seed, B, nh, T, p):
+    """The attention kernels' dropout keep-mask (B, nh, T, T) bool: element ((b*nh + h)*T + i)*T + j."""
+    keep = dropout_keep(seed, np.arange(B * nh * T * T, dtype=np.uint64), p)
+    return torch.from_numpy(keep.reshape(B, nh, T, T))
+
+
+def rel_fro(got, ref):
+    """|got - ref|_F / |ref|_F in double (0 when both vanish)."""
+    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
+    n = float(ref.norm())
+    e = float((got - ref).norm())
+    return e / n if n > 0 else e
+
+
+# The cases of tests/test_attn_train_gpu.py; tests/test_kernel_refs_cpu.py checks on the CPU that each reaches the
+# rescale path (or, for ``flat``, does not) and is well enough conditioned.  (regime, B, nh, T, hs, dtype)
+ATTN_MFMA_CASES = [(r, 2, nh, T, 64, torch.bfloat16) for nh in (2, 3) for T in (129, 200, 257) for r in ATTN_REGIMES]
+# ramp at hs 16 runs at T = 130 only: at T = 70 it has too few tiles with a large step of the running max
+ATTN_VALU_CASES = [(r, 2, 2, T, hs, dt)
+                   for hs, dt in ((16, torch.float32), (64, torch.float32), (12, torch.float32), (32, torch.bfloat16))
+                   for T in (70, 130) for r in ATTN_REGIMES if not (r == "ramp" and hs == 16 and T == 70)]
+ATTN_DROP_CASES = [("big", 2, 2, 130, 64, torch.bfloat16), ("big", 2, 2, 70, 32, torch.bfloat16),
+                   ("big", 2, 2, 130, 12, torch.float32)]
+ATTN_DROP_P, ATTN_DROP_SEED = 0.2, 12345
+
+
+def attn_case_seed(B, nh, T, hs):
+    """Seed of a case's inputs.  The offsets at hs 12 and hs 32 move on from draws whose T = 70 case missed an event
+    count that tests/test_kernel_refs_cpu.py requires (flat: 47 and 41 stale tiles; big at hs 32: 13 rescales)."""
+    return 1000 + T + hs + 17 * (nh - 2) + {12: 2, 32: 1}.get(hs, 0)
+
+
+def attn_case_id(c):
+    return f"{c[0]}-nh{c[2]}-T{c[3]}-hs{c[4]}-{'bf16' if c[5] == torch.bfloat16 else 'f32'}"
 
 
 # ------------------------------------------------------------------------------------------ comparison bars

@@ -1,5 +1,5 @@
-"""Causal attention kernels (aw_attn_fwd / aw_attn_bwd) against a plain torch fp32 reference of
-CausalSelfAttention (model/transformer_block.py:37-63, attention dropout 0).  fp32 operands -> the VALU
+"""Causal attention kernels (aw_attn_fwd / aw_attn_bwd) against the fp64 reference of CausalSelfAttention
+(kernel_refs.attn_train_ref; model/transformer_block.py:37-63, attention dropout 0).  fp32 operands -> the VALU
 kernels (tolerance 1e-4); bf16 operands -> the MFMA kernels at head size 64 (VALU otherwise), compared on the
 same bf16-rounded inputs with bf16-output tolerance."""
 import math
@@ -11,21 +11,10 @@ pytestmark = pytest.mark.gpu
 
 
 def reference(qkv, B, T, nh, d, dy):
-    q, k, v = qkv.float().view(B, T, 3 * d).split(d, dim=2)
-    hs = d // nh
-    q = q.reshape(B, T, nh, hs).transpose(1, 2).requires_grad_()
-    k = k.reshape(B, T, nh, hs).transpose(1, 2).requires_grad_()
-    v = v.reshape(B, T, nh, hs).transpose(1, 2).requires_grad_()
-    att = (q @ k.transpose(-2, -1)) / math.sqrt(hs)
-    mask = torch.tril(torch.ones(T, T, device=qkv.device, dtype=torch.bool))
-    att = att.masked_fill(~mask, float("-inf"))
-    lse = torch.logsumexp(att, dim=-1)
-    y = (torch.softmax(att, dim=-1) @ v).transpose(1, 2).reshape(B * T, d)
-    y.backward(dy.float())
-    dq = q.grad.transpose(1, 2).reshape(B * T, d)
-    dk = k.grad.transpose(1, 2).reshape(B * T, d)
-    dv = v.grad.transpose(1, 2).reshape(B * T, d)
-    return y.detach(), lse.detach().reshape(-1), torch.cat([dq, dk, dv], dim=1)
+    """kernel_refs.attn_train_ref (fp64, on the device) as f32: y, lse and dqkv."""
+    from kernel_refs import attn_train_ref
+    y, lse, dqkv, _ = attn_train_ref(qkv, dy, B, T, nh, d)
+    return y.float(), lse.float(), dqkv.float()
 
 
 def run(qkv, B, T, nh, d, dy):
