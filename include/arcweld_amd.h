@@ -818,6 +818,37 @@ typedef struct {
 } aw_ensemble_args;
 int aw_ensemble_stats(const aw_ensemble_args* args, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ k-NN search
+ * Brute-force exact k-nearest-neighbour search in squared Euclidean distance, f32 throughout (arcweld.retrieve): the
+ * (nq x nx) distance matrix is never written to memory.
+ * q: (nq, d) f32 queries, rows ldq >= d floats apart; x: (nx, d) f32 database, rows ldx >= d apart; any 4-byte aligned
+ * base (16-byte loads when base and stride are 16-byte aligned, guarded 4-byte loads otherwise); the row padding and
+ * the rows past the end are never read.  idx (nq, k) int64 and dist (nq, k) f32, compact, nearest first.
+ *   - d(i, j) = fl(fl(|q_i|^2 + |x_j|^2) - 2 dot(q_i, x_j)); the norms are in-order fmaf chains over the dims, the dot
+ *     products run on the f32-input MFMA (exact f32) in one fixed order over d, always inside one workgroup: the bits
+ *     of a distance depend on neither the launch geometry nor the run.  No bf16 operand mode exists.
+ *   - candidates are ranked lexicographically by (d as computed, j): the lower database index wins a tie.  Only a
+ *     finite d is ever taken: a NaN or +inf distance (NaN / inf rows, f32 overflow) never appears as a neighbour.
+ *   - the stored distance is max(d, 0); the clamp never touches the ranking.
+ *   - q_group (nq) / x_group (nx) int32, each optional: row j is skipped for query i when q_group[i] == x_group[j];
+ *     a NULL on either side means no exclusion (leave-one-out of a set against itself: group = row index).
+ *   - with fewer than k eligible rows the remaining slots hold idx = -1 and dist = +inf.
+ * Grid: (query tiles) x (database splits); every split writes its partial lists to the workspace and a second kernel
+ * merges splits * k candidates per query in the same (d, j) order, so the result is bit-identical for every split
+ * count.  splits = 0 picks the count that fills the device; ws needs aw_knn_workspace(nq, nx, d, k, splits) bytes
+ * (4-byte aligned).  aw_knn_describe reports the tile sizes (queries per workgroup, database rows per tile, dims per
+ * chunk) and AW_KNN_MAX_K.
+ * AW_ERR_ARG and no launch (aw_knn_workspace returns AW_ERR_ARG): nq < 0, nx outside 0..2^31 - 1, d < 1, k outside
+ * 1..AW_KNN_MAX_K, splits outside 0..AW_KNN_MAX_SPLITS, a stride below d or above 2^22 - 1, a NULL q / idx / dist, a
+ * workspace that is too small.  nq == 0: AW_OK, nothing launched; nx == 0: every slot is (-1, +inf). */
+#define AW_KNN_MAX_K 32
+#define AW_KNN_MAX_SPLITS 1024
+int64_t aw_knn_workspace(int64_t nq, int64_t nx, int d, int k, int splits);
+int aw_knn(const float* q, int64_t nq, int64_t ldq, const float* x, int64_t nx, int64_t ldx, int d, int k,
+           const int* q_group, const int* x_group, int splits /* 0 = auto */, void* ws, int64_t ws_bytes, int64_t* idx,
+           float* dist, void* stream);
+int aw_knn_describe(int* tile_q, int* tile_x, int* chunk_d, int* max_k);
+
 #ifdef __cplusplus
 }
 #endif

@@ -122,6 +122,8 @@ class BeamArgs(ctypes.Structure):
 
 ENSEMBLE_MAX_N = 64   # AW_ENSEMBLE_MAX_N
 ENSEMBLE_MAX_Q = 8    # AW_ENSEMBLE_MAX_Q
+KNN_MAX_K = 32        # AW_KNN_MAX_K
+KNN_MAX_SPLITS = 1024  # AW_KNN_MAX_SPLITS
 
 
 class EnsembleArgs(ctypes.Structure):
@@ -241,9 +243,12 @@ SIGNATURES = {
     "aw_score_rows": [c_p, c_i64, c_int, c_int, c_p, c_i64, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p],
     "aw_window_sqerr": [c_p, c_p, c_p, c_i64, c_i64, c_int, c_int, c_p, c_p, c_p],
     "aw_ensemble_stats": [ctypes.POINTER(EnsembleArgs), c_p],
+    "aw_knn_workspace": [c_i64, c_i64, c_int, c_int, c_int],
+    "aw_knn": [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_int, c_int, c_p, c_p, c_int, c_p, c_i64, c_p, c_p, c_p],
+    "aw_knn_describe": [ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)],
 }
 
-RET_I64 = {"aw_gemm_workspace", "aw_wgrad_batch_workspace", "aw_res_dropout_masks_bytes"}
+RET_I64 = {"aw_gemm_workspace", "aw_wgrad_batch_workspace", "aw_res_dropout_masks_bytes", "aw_knn_workspace"}
 
 _lib = None
 

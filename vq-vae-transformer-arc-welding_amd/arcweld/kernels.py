@@ -796,6 +796,54 @@ def ensemble_stats(x, q, mean=None, std=None, quant=None, y=None, seg=None, crps
     call("aw_ensemble_stats", ctypes.byref(a), stream_ptr(stream))
 
 
+def knn_describe():
+    """aw_knn_describe: (tile_q, tile_x, chunk_d, max_k) of the k-NN kernel (the tests aim at the tile edges)."""
+    v = [nat.c_int(0) for _ in range(4)]
+    call("aw_knn_describe", *[ctypes.byref(c) for c in v])
+    return tuple(int(c.value) for c in v)
+
+
+def knn(q, x, k, q_group=None, x_group=None, splits=None, idx=None, dist=None, stream=None):
+    """aw_knn: the k nearest rows of x (nx, D) for every row of q (nq, D) in squared Euclidean distance, f32, ranked by
+    (distance, index); see include/arcweld_amd.h.  q, x: f32 device tensors with contiguous rows (any row stride >= D,
+    any 4-byte aligned base).  q_group (nq) / x_group (nx): optional int32, equal groups are skipped.  splits None or
+    0: the library picks the database split count.  Returns (idx (nq, k) int64, dist (nq, k) f32); slots past the
+    eligible rows hold (-1, +inf).  The ranges of k and splits are the library's to refuse."""
+    for nm, t in (("q", q), ("x", x)):
+        if t.dim() != 2 or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1) or not t.is_cuda:
+            raise nat.NativeError(f"knn: {nm} must be a 2-d float32 device tensor with contiguous rows, got "
+                                  f"{t.dtype} {tuple(t.shape)} strides {tuple(t.stride())}")
+    nq, D = q.shape
+    nx = x.shape[0]
+    if x.shape[1] != D or D < 1:
+        raise nat.NativeError(f"knn: q has {D} features, x has {x.shape[1]}; need the same D >= 1")
+    k = int(k)
+    ldq = max(q.stride(0), D) if nq > 1 else D
+    ldx = max(x.stride(0), D) if nx > 1 else D
+    for nm, g, n in (("q_group", q_group, nq), ("x_group", x_group, nx)):
+        if g is not None and (g.dtype != torch.int32 or tuple(g.shape) != (n,) or not g.is_contiguous()
+                              or g.device != q.device):
+            raise nat.NativeError(f"knn: {nm} must be a contiguous int32 tensor of {n} elements on q's device")
+    sp = 0 if splits is None else int(splits)
+    if idx is None:
+        idx = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=q.device)
+    if dist is None:
+        dist = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=q.device)
+    for nm, t, dt in (("idx", idx, torch.int64), ("dist", dist, torch.float32)):
+        if t.dtype != dt or tuple(t.shape) != (nq, k) or not t.is_contiguous() or t.device != q.device:
+            raise nat.NativeError(f"knn: {nm} must be a contiguous {dt} tensor of shape {(nq, k)} on q's device")
+    lib = nat.load()
+    ws_bytes = lib.aw_knn_workspace(nq, nx, D, k, sp)
+    if ws_bytes < 0:
+        raise nat.NativeError(f"aw_knn_workspace failed ({ws_bytes}): {lib.aw_last_error().decode(errors='replace')}")
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=q.device)
+    _maybe_timed(stream, "knn", 2.0 * nq * nx * D, lambda s: call(
+        "aw_knn", ptr(q), nq, ldq, ptr(x) if nx else None, nx, ldx, D, k, ptr(q_group), ptr(x_group), sp, ptr(ws),
+        ws.numel(), ptr(idx), ptr(dist), s),
+        info=lambda: (f"knn_sweep_kernel k={k} D={D}", 4.0 * (nq + nx) * D + 12.0 * nq * k))
+    return idx, dist
+
+
 # ------------------------------------------------------------------------------------------ layouts
 def patchify(x, P, out, stream=None):
     B, L, C = x.shape

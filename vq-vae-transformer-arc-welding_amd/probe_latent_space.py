@@ -1,0 +1,95 @@
+"""k-NN probe of a latent space: how well can weld quality be read off the features, without training anything.
+
+The train split is the database, val and test are the queries (arcweld.retrieve.latent_knn_probe): every query
+sequence takes the label its ``--k`` nearest training sequences vote for, after the StandardScaler of the reference's
+fit_knn protocol (``--no-standardize`` switches it off).  ``--dataset latent_vq_vae`` probes the latent vectors of the
+frozen VQ-VAE given by ``--vqvae-model`` -- the features train_classification_model.py fits its GRU on --,
+``--dataset asimow`` the raw current / voltage cycles.  The search runs on the device (csrc/knn.hip) and takes seconds.
+
+Data: synthetic welding sequences of n_cycles 200x2 windows with random labels, or ``--data-npz`` in the layout
+train_classification_model.py reads ('train' / 'val' / 'test' of shape (n, n_cycles*200, 2) and '<split>_labels'),
+with optional '<split>_groups' (integer ids, e.g. the welding run): a query never takes a neighbour of its own group.
+``--loo`` adds the train split against itself, each sequence (or, with 'train_groups', each group) left out of its own
+neighbours.
+
+``--out`` receives the metrics as JSON: {"val" / "test" / "train_loo": {"acc", "acc_good", "acc_bad", "f1"}, "k",
+"weights", "dataset", "standardize", "n_cycles"}.  ``--neighbours-out`` (optional) receives an .npz with
+'<split>_idx' (n, k) int64, '<split>_dist' (n, k) f32 (squared distances; -1 / +inf past the eligible rows) and
+'<split>_pred' (n,) int64 per split.
+"""
+import argparse
+import json
+import logging as log
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from generate_welding_cycles import require_checkpoint  # noqa: E402
+
+METRICS = ("acc", "acc_good", "acc_bad", "f1")
+
+
+def parser():
+    p = argparse.ArgumentParser(description='Probe-Latent-Space')
+    p.add_argument('--vqvae-model', type=str, help='Path of the VQ-VAE checkpoint',
+                   default="model_checkpoints/VQ-VAE-Patch/vq_vae_patch_best_02.ckpt")
+    p.add_argument('--dataset', choices=["latent_vq_vae", "asimow"], default="latent_vq_vae")
+    p.add_argument('--n-cycles', type=int, help='Number of cycles', default=5)
+    p.add_argument('--k', type=int, help='Neighbours per query', default=1)
+    p.add_argument('--weights', choices=["uniform", "distance"], default="uniform")
+    p.add_argument('--no-standardize', action='store_true', help="search the features as they are")
+    p.add_argument('--loo', action='store_true', help="also: the train split against itself, leave-one-out")
+    p.add_argument('--data-npz', type=str, default="")
+    p.add_argument('--n-train', type=int, default=1024)
+    p.add_argument('--n-val', type=int, default=128)
+    p.add_argument('--n-test', type=int, default=128)
+    p.add_argument('--seed', type=int, default=0)
+    p.add_argument('--out', type=str, default="latent_probe.json")
+    p.add_argument('--neighbours-out', type=str, default="")
+    return p
+
+
+def load_groups(path):
+    """{'train' / 'val' / 'test': ids} for the '<split>_groups' arrays the .npz holds (none: {})."""
+    if not path:
+        return {}
+    with np.load(path, allow_pickle=False) as f:
+        return {k: torch.tensor(f[k + "_groups"], dtype=torch.long) for k in ("train", "val", "test")
+                if k + "_groups" in f.files}
+
+
+def main(hparams):
+    if hparams.dataset == "latent_vq_vae":
+        require_checkpoint(hparams.vqvae_model, "--vqvae-model")
+    if hparams.n_cycles < 1:
+        raise SystemExit("--n-cycles must be at least 1")
+    from arcweld.retrieve import MAX_K, latent_knn_probe
+    if not 1 <= hparams.k <= MAX_K:
+        raise SystemExit(f"--k must lie in 1..{MAX_K}")
+    from train_transformer_mtasks import load_splits, load_vqvae
+    dev = torch.device("cuda", torch.cuda.current_device())
+    vqvae = load_vqvae(hparams.vqvae_model, dev) if hparams.dataset == "latent_vq_vae" else None
+    res = latent_knn_probe(load_splits(hparams, dev), hparams.n_cycles, k=hparams.k, dataset=hparams.dataset,
+                           vqvae=vqvae, weights=hparams.weights, standardize=not hparams.no_standardize,
+                           loo=hparams.loo, groups=load_groups(hparams.data_npz))
+    summary = {name: {m: r[m] for m in METRICS} for name, r in res.items()}
+    summary.update(k=hparams.k, weights=hparams.weights, dataset=hparams.dataset,
+                   standardize=not hparams.no_standardize, n_cycles=hparams.n_cycles)
+    with open(hparams.out, "w") as f:
+        json.dump(summary, f, indent=1, sort_keys=True)
+    if hparams.neighbours_out:
+        np.savez(hparams.neighbours_out, **{f"{name}_{key}": r[key].cpu().numpy() for name, r in res.items()
+                                            for key in ("idx", "dist", "pred")})
+    for name, r in res.items():
+        log.info(f"{name}: " + ", ".join(f"{m} {r[m]:.4f}" for m in METRICS))
+    return res
+
+
+if __name__ == '__main__':
+    args = parser().parse_args()
+    log.basicConfig(level=log.INFO, format='%(asctime)s - %(levelname)s - %(message)s')
+    main(args)
