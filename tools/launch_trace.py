@@ -8,8 +8,11 @@ dtype, strides); the ordinal is given at first appearance, keyed by storage poin
 every tensor it has seen alive, so that no storage is reused: two same-shaped tensors swapped between roles change the
 trace.  A host-side refactor of the drivers must leave every digest as it was:
 
-    python tools/launch_trace.py --tree <parent checkout>
-    python tools/launch_trace.py                             # this tree; --json FILE keeps the full records
+    python tools/launch_trace.py --tree <parent checkout> --digests parent.json
+    python tools/launch_trace.py --digests new.json          # this tree; --json FILE keeps the full records
+
+``--digests FILE`` writes {case: {path: digest}}; tests/golden/launch_trace.json is that file, and
+tests/test_launch_trace_cpu.py compares a few cases (``--cases NAME ...``) against it.
 """
 import argparse
 import hashlib
@@ -20,7 +23,11 @@ import sys
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REAL = {"res_chain_ok", "convt_tail_ok", "sep_tail_ok", "chain_head_ok", "head_bf16_ok", "wgrad_issue", "wgrad_batch_ok", "attn_flops"}
-PATHS = ("fused_train_step", "autograd", "eval", "encode", "encoder[0]", "decoder[1]", "resblock")
+PATHS = ("fused_train_step", "autograd", "eval", "encode", "encoder[0]", "decoder[1]", "resblock", "decode",
+         "decode_small", "patch_embed", "encoder[1]", "reverse_patch_embed", "reverse_patch_embed_eval")
+# the route switches of the boundary layers, one at a time and the first three together (bf16 bn=0, R in (1, 3))
+ROUTES_OFF = ("ARCWELD_CONVT_TAIL", "ARCWELD_SEP_TAIL", "ARCWELD_CHAIN_HEAD")
+ROUTE_ENVS = [{k: "0"} for k in ROUTES_OFF + ("ARCWELD_HEAD_BF16",)] + [{k: "0" for k in ROUTES_OFF}]
 ENV = ("ARCWELD_ENC_CHAIN", "ARCWELD_DEC_CHAIN", "ARCWELD_RESID_F32", "ARCWELD_HEAD_BF16", "ARCWELD_CHAIN_STORE",
        "ARCWELD_WGRAD_BATCH", "ARCWELD_OPERANDS", "ARCWELD_CONVT_TAIL", "ARCWELD_SEP_TAIL",
        "ARCWELD_CHAIN_HEAD")
@@ -92,6 +99,11 @@ def cases():
                 for R in (0, 1, 3):
                     for p in (0.1, 0.0):
                         yield dict(T=T, bn=bn, R=R, p=p, env=env, batch=False)
+            if T == "bf16" and not bn:
+                for env in ROUTE_ENVS:
+                    for R in (1, 3):
+                        for p in (0.1, 0.0):
+                            yield dict(T=T, bn=bn, R=R, p=p, env=env, batch=False)
     yield dict(T="bf16", bn=False, R=3, p=0.1, env={}, batch=True)
 
 
@@ -136,6 +148,18 @@ def run_case(c, rec, torch):
             xx = torch.randn(4, 512, L, requires_grad=True)
             mod(xx).sum().backward()
             out[name] = rec.take()
+        # ids -> signals: S = 16, K = 512, so 64 ids take the codebook-table branch and 16 the gather-then-GEMM one
+        for name, n in (("decode", 64), ("decode_small", 16)):
+            engine.decode(m, torch.arange(n) * 7 % 512, T)
+            out[name] = rec.take()
+        for name, mod, shape, train in (("patch_embed", m.patch_embed, (4, 200, 2), True),
+                                        ("encoder[1]", m.encoder[1], (4, 512, 16), True),
+                                        ("reverse_patch_embed", m.reverse_patch_embed, (4, 512, 16), True),
+                                        ("reverse_patch_embed_eval", m.reverse_patch_embed, (4, 512, 16), False)):
+            m.train(train)
+            xx = torch.randn(*shape, requires_grad=True)
+            mod(xx).sum().backward()
+            out[name] = rec.take()
     for k in c["env"]:
         os.environ.pop(k)
     return out
@@ -149,6 +173,8 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--tree", default=HERE, help="the checkout to import arcweld / model from (default: this one)")
     ap.add_argument("--json", help="write the full records of every case to this file")
+    ap.add_argument("--digests", help="write {case: {path: digest}} of every case to this file")
+    ap.add_argument("--cases", nargs="+", metavar="NAME", help="run only the cases of these names (as printed)")
     a = ap.parse_args()
     tree = os.path.abspath(a.tree)
     sys.path[:0] = [tree, os.path.join(tree, "vq-vae-transformer-arc-welding_amd")]
@@ -157,7 +183,10 @@ def main():
     rec = Recorder(K, torch)
     full = {}
     print(f"{'case':44s} " + " ".join(f"{p[:10]:>10s}" for p in PATHS) + "  digest")
-    for c in cases():
+    todo = [c for c in cases() if a.cases is None or case_name(c) in a.cases]
+    if a.cases is not None and len(todo) != len(set(a.cases)):
+        ap.error(f"unknown case among {a.cases}")
+    for c in todo:
         out = run_case(c, rec, torch)
         full[case_name(c)] = out
         print(f"{case_name(c):44s} " + " ".join(f"{len(out[p]):10d}" for p in PATHS) + f"  {digest(out)}")
@@ -165,6 +194,10 @@ def main():
     if a.json:
         with open(a.json, "w") as f:
             json.dump(full, f, indent=0)
+    if a.digests:
+        with open(a.digests, "w") as f:
+            json.dump({name: {p: digest(v) for p, v in out.items()} for name, out in full.items()}, f, indent=1)
+            f.write("\n")
 
 
 if __name__ == "__main__":

@@ -23,7 +23,8 @@ import torch
 
 from . import kernels as K
 from . import operands
-from .vqvae import _mix, operand_dtype, rng_snapshot
+from .boundary import mix
+from .vqvae import operand_dtype, rng_snapshot
 
 F32 = torch.float32
 
@@ -91,9 +92,9 @@ def forward(m, ids, generate: bool, training: bool, need_backward: bool, seed: i
     nb = len(m.transformer.h)
     # attention-probability dropout (CausalSelfAttention.attn_dropout; reference default 0.0)
     sv.p_att = float(m.transformer.h[0].attn.attn_pdrop) if (training and nb) else 0.0
-    sv.seed_attn = [_mix(seed, 300 + i) for i in range(nb)]
-    sv.seed_mlp = [_mix(seed, 400 + i) for i in range(nb)]
-    sv.seed_probs = [_mix(seed, 500 + i) for i in range(nb)]
+    sv.seed_attn = [mix(seed, 300 + i) for i in range(nb)]
+    sv.seed_mlp = [mix(seed, 400 + i) for i in range(nb)]
+    sv.seed_probs = [mix(seed, 500 + i) for i in range(nb)]
     sv.ctr = rng_snapshot(m, dev, max(p_drop, sv.p_att), zero=zero)   # zero: a caller's f64 accumulators
     ids = ids.contiguous()
 

@@ -4,8 +4,9 @@ PatchEmbeddingInverse, Block, LatentEmbedding(Cond).
 The training entry points run whole models as one fused node (arcweld.vqvae / arcweld.decoder); the reference's
 sub-modules are ordinary autograd modules as well (model/vq_vae_patch_embedd.py:7-114, model/transformer_block.py,
 model/embedding.py), so each one here has its own forward (saving what its backward reads) and backward on the same
-HIP kernels -- the per-block pieces of the fused passes, with the weight operands built per call (the persistent,
-optimizer-maintained copies belong to the fused models).
+HIP kernels.  The VQ-VAE pieces issue the launches the fused passes issue, through the same host modules
+(arcweld.resstack, arcweld.boundary); what is theirs is the layout conversion at either end and the weight operands,
+built per call (the persistent, optimizer-maintained copies belong to the fused models).
 
 Every function takes and returns the reference's layouts: (B, C, S) channel-major for the conv blocks, (B, T, d) for
 the transformer block.  Dropout draws a fresh host seed per call (the masks are counter-based; the backward
@@ -15,9 +16,11 @@ from __future__ import annotations
 
 import torch
 
+from . import boundary
 from . import kernels as K
 from . import resstack
-from .vqvae import _biases, _grads, _mix, operand_dtype
+from .boundary import cast, mix
+from .precision import operand_dtype
 
 F32 = torch.float32
 
@@ -42,30 +45,13 @@ def _channel_major(t_nc, B, S):
     return t_nc.view(B, S, -1).permute(0, 2, 1)
 
 
-def _masked_copy(g, T, p, seed):
-    """Operand copy of g [N][H] (dtype T) with the dropout mask of (p, seed) applied: the GEMM epilogue over an
-    empty contraction (v = 0 + resid, C2 = mask(v))."""
-    N, H = g.shape
-    out = torch.empty(N, H, device=g.device, dtype=T)
-    dummy = torch.zeros(8, 8, device=g.device, dtype=T)
-    K.gemm(dummy, dummy, N, H, 0, resid=g, C2=out, c2_mode=3, drop2=(p, seed))
-    return out
-
-
-def _gelu_operand(x, T):
-    """Operand copy of GELU(x) (dtype T), by the same empty-contraction epilogue (C2 = gelu(v))."""
-    N, H = x.shape
-    out = torch.empty(N, H, device=x.device, dtype=T)
-    dummy = torch.zeros(8, 8, device=x.device, dtype=T)
-    K.gemm(dummy, dummy, N, H, 0, resid=x, C2=out, c2_mode=1)
-    return out
-
-
-def _cast(t, T):
-    if t.dtype == T:
-        return t.contiguous()
-    out = torch.empty(t.shape, device=t.device, dtype=T)
-    K.cast(t.contiguous(), out)
+def _operand_copy(v, T, c2_mode, drop2=(0.0, 0)):
+    """Operand copy (dtype T) of v [N][H] through the GEMM epilogue over an empty contraction (0 + resid): GELU(v)
+    (c2_mode 1), or v under the dropout mask of drop2 = (p, seed) (c2_mode 3)."""
+    N, H = v.shape
+    out = torch.empty(N, H, device=v.device, dtype=T)
+    dummy = torch.zeros(8, 8, device=v.device, dtype=T)
+    K.gemm(dummy, dummy, N, H, 0, resid=v, C2=out, c2_mode=c2_mode, drop2=drop2)
     return out
 
 
@@ -131,21 +117,17 @@ def patch_embed(mod, x):
         W = torch.zeros(H, ldp, device=x.device, dtype=T)
         K.weight_relayout(mod.proj.weight, H, 1, P, 0, 4, W, ldo=ldp)
         out = e(B * S, H)
-        K.gemm(patches, W, B * S, H, ldp, bias=mod.proj.bias, C=out)
-        sv = _Saved()
-        sv.shape, sv.patches, sv.W, sv.ldp = (B, L, C, S), patches, W, ldp
-        return _channel_major(out, B, S), sv
+        boundary.conv_fwd(patches, W, mod.proj.bias, out)
+        return _channel_major(out, B, S), ((B, L, C), patches, W)
 
     def bwd(sv, g, slot, need_x):
-        B, L, C, S = sv.shape
-        N = B * S
+        (B, L, C), patches, W = sv
         gt = _tokens(g, T)
-        K.gemm(gt, sv.patches, H, P, N, a_trans=True, b_trans=True, C=slot(mod.proj.weight).view(H, P),
-               accumulate=True, a_rowsum=slot(mod.proj.bias))
+        boundary.conv_wgrad(gt, patches, slot(mod.proj.weight).view(H, P), slot(mod.proj.bias))
         if not need_x:
             return None
-        gp = torch.empty(N, sv.ldp, device=g.device)
-        K.gemm(gt, sv.W, N, sv.ldp, H, b_trans=True, C=gp)
+        gp = torch.empty(patches.shape, device=g.device)
+        boundary.conv_dgrad(gt, W, gp)
         # patches[b*S + t][j] = x[b, l, c] with t*P + j = c*L + l: the inverse is a view of the patch rows
         return gp[:, :P].reshape(B, C, L).permute(0, 2, 1).contiguous()
 
@@ -181,20 +163,20 @@ def _resblock_stack(mod, blocks, sep, batch_norm, dropout_p, x):
         p = dropout_p if mod.training else 0.0
         seed = _seed(p)
         cur = _tokens(x, F32)
-        a0 = _gelu_operand(cur, T)
+        a0 = _operand_copy(cur, T, 1)
         weights = _BlockOperands(convs, geo.fwd_job, (H, geo.Kd), T)
-        y, _, rec = resstack.forward(geo, cur, a0, weights, _biases(convs), bns, T=T, RT=F32, p_drop=p,
-                                     seeds=[_mix(seed, r) for r in range(len(blocks))], training=mod.training,
+        y, _, rec = resstack.forward(geo, cur, a0, weights, resstack.biases(convs), bns, T=T, RT=F32, p_drop=p,
+                                     seeds=[mix(seed, r) for r in range(len(blocks))], training=mod.training,
                                      last_operand_only=False, save=save)
         return _channel_major(y, B, S), ((B, H, S), rec)
 
     def bwd(sv, g, slot, need_x):
         (B, H, S), rec = sv
         gy = _tokens(g, F32)
-        go = _masked_copy(gy, T, rec.p_drop, rec.seeds[-1]) if (blocks and not batch_norm) else None
+        go = _operand_copy(gy, T, 3, (rec.p_drop, rec.seeds[-1])) if (blocks and not batch_norm) else None
         # per-token convs: the forward's operands serve; k = 3: the dgrad operands [3O][I]
         dweights = rec.ws if sep else _BlockOperands(convs, rec.geo.dgrad_job, (3 * H, H), T)
-        gy, _, wgrads = resstack.backward(rec, gy, go, dweights, _grads(convs, slot), bns, slot, r0_copy=False)
+        gy, _, wgrads = resstack.backward(rec, gy, go, dweights, resstack.grads(convs, slot), bns, slot, r0_copy=False)
         K.gemm_grouped(wgrads)
         if not need_x:
             return None
@@ -232,21 +214,17 @@ def sep_cnn(mod, x):
         W = torch.empty(D, H, device=x.device, dtype=T)
         K.weight_relayout(conv.weight, D, H, 1, 0, 0, W)
         z = torch.empty(N, D, device=x.device)
-        K.gemm(xt, W, N, D, H, bias=conv.bias, C=z)
-        sv = _Saved()
-        sv.shape, sv.xt, sv.W = (B, H, S), xt, W
-        return z.view(B, S, D), sv
+        boundary.conv_fwd(xt, W, conv.bias, z)
+        return z.view(B, S, D), ((B, H, S), xt, W)
 
     def bwd(sv, g, slot, need_x):
-        B, H, S = sv.shape
-        N = B * S
-        gz = _cast(g.reshape(N, D), T)
-        K.gemm(gz, sv.xt, D, H, N, a_trans=True, b_trans=True, C=slot(conv.weight).view(D, H), accumulate=True,
-               a_rowsum=slot(conv.bias))
+        (B, H, S), xt, W = sv
+        gz = cast(g.reshape(B * S, D), T)
+        boundary.conv_wgrad(gz, xt, slot(conv.weight).view(D, H), slot(conv.bias))
         if not need_x:
             return None
-        gx = torch.empty(N, H, device=g.device)
-        K.gemm(gz, sv.W, N, H, D, b_trans=True, C=gx)
+        gx = torch.empty(B * S, H, device=g.device)
+        boundary.conv_dgrad(gz, W, gx)
         return _channel_major(gx, B, S).contiguous()
 
     return run(mod, fwd, bwd, x)
@@ -270,37 +248,18 @@ def patch_unembed(mod, x):
         Y = e(N, k1 * H)
         training = mod.training
         cs = torch.zeros(2 * H, device=x.device, dtype=torch.float64) if training else None
-        K.gemm(xt, W, N, k1 * H, H, bias=t1.bias, bias_mod=H, C=Y, colstats=cs, stats_mod=H)
-        stats = e(4 * H)
-        K.bn_finalize(cs, N * k1, H, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                      bn.num_batches_tracked if training else None, bn.eps,
-                      bn.momentum if bn.momentum is not None else 0.1, training, stats)
         Q = S * k1
         out = e(B, Q * 5 // mod.input_dim, mod.input_dim)
-        K.unpatch_head_fwd(Y.view(N * k1, H), Q, stats, t2.weight.view(H, 5), t2.bias, out)
-        sv = _Saved()
-        sv.shape, sv.xt, sv.W, sv.Y, sv.stats, sv.training = (B, H, S), xt, W, Y, stats, training
-        return out, sv
+        stats = boundary.unpatch_fwd(xt, W, t1, bn, t2, Y, Q, out, training=training, colstats=cs, stats_mod=H)
+        return out, ((B, H, S), xt, W, Y, stats, training)
 
     def bwd(sv, g, slot, need_x):
-        B, H, S = sv.shape
-        N = B * S
-        e = _empty(g.device)
-        Y2 = sv.Y.view(N * k1, H)
+        (B, H, S), xt, W, Y, stats, training = sv
         gsums = torch.zeros(2 * H, device=g.device, dtype=torch.float64)
-        w2 = t2.weight.view(H, 5)
-        K.unpatch_head_bwd1(Y2, S * k1, sv.stats, w2, g, gsums, slot(t2.weight).view(H, 5), slot(t2.bias),
-                            slot(bn.weight), slot(bn.bias))
-        gY = e(N * k1, H, dt=T)
-        K.unpatch_head_bwd2(Y2, S * k1, sv.stats, w2, g, gsums, sv.training, gY, slot(t1.bias))
-        gY2 = gY.view(N, k1 * H)
-        K.gemm(sv.xt, gY2, H, k1 * H, N, a_trans=True, b_trans=True, C=slot(t1.weight).view(H, H * k1),
-               accumulate=True, col_map=(H, k1, 0))
-        if not need_x:
-            return None
-        gx = e(N, H)
-        K.gemm(gY2, sv.W, N, H, k1 * H, b_trans=True, C=gx)
-        return _channel_major(gx, B, S).contiguous()
+        gx = torch.empty(B * S, H, device=g.device) if need_x else None
+        boundary.unpatch_bwd(xt, W, t1, bn, t2, Y.view(-1, H), S * k1, stats, g, gsums, slot, T, training=training,
+                             gx=gx)
+        return _channel_major(gx, B, S).contiguous() if need_x else None
 
     return run(mod, fwd, bwd, x)
 
@@ -321,8 +280,8 @@ def causal_self_attention(mod, x):
         p = float(mod.resid_dropout.p) if training else 0.0
         pa = float(mod.attn_pdrop) if training else 0.0
         s_res, s_probs = _seed(p), _seed(pa)
-        xa = _cast(x.reshape(R, d), Td)
-        Wqkv, Wo = _cast(mod.c_attn.weight, Td), _cast(mod.c_proj.weight, Td)
+        xa = cast(x.reshape(R, d), Td)
+        Wqkv, Wo = cast(mod.c_attn.weight, Td), cast(mod.c_proj.weight, Td)
         qkv = e(R, 3 * d, dt=Td)
         K.gemm(xa, Wqkv, R, 3 * d, d, bias=mod.c_attn.bias, C=qkv)
         y, lse = e(R, d, dt=Td), e(B * nh * T)
@@ -341,7 +300,7 @@ def causal_self_attention(mod, x):
         e = _empty(g.device)
         c = sv.c
         s_res, s_probs = sv.seeds
-        go = _masked_copy(g.reshape(R, d).float().contiguous(), Td, sv.p, s_res)
+        go = _operand_copy(g.reshape(R, d).float().contiguous(), Td, 3, (sv.p, s_res))
         gy = e(R, d, dt=Td)
         K.gemm(go, c["Wo"], R, d, d, b_trans=True, C=gy)
         K.gemm(go, c["y"], d, d, R, a_trans=True, b_trans=True, C=slot(mod.c_proj.weight), accumulate=True,
@@ -373,8 +332,8 @@ def mlp(mod, x):
         training = mod.training
         p = float(mod["dropout"].p) if training else 0.0
         s = _seed(p)
-        xa = _cast(x.reshape(R, d), Td)
-        Wfc, Wp = _cast(mod["c_fc"].weight, Td), _cast(mod["c_proj"].weight, Td)
+        xa = cast(x.reshape(R, d), Td)
+        Wfc, Wp = cast(mod["c_fc"].weight, Td), cast(mod["c_proj"].weight, Td)
         dh = Wfc.shape[0]
         h, gl = e(R, dh, dt=Td), e(R, dh, dt=Td)
         K.gemm(xa, Wfc, R, dh, d, bias=mod["c_fc"].bias, act=K.AW_ACT_GELU_TANH, C=h, C2=gl, c2_mode=1)
@@ -392,7 +351,7 @@ def mlp(mod, x):
         e = _empty(g.device)
         c = sv.c
         dh = c["Wfc"].shape[0]
-        go = _masked_copy(g.reshape(R, d).float().contiguous(), Td, sv.p, sv.seed)
+        go = _operand_copy(g.reshape(R, d).float().contiguous(), Td, 3, (sv.p, sv.seed))
         gh = e(R, dh, dt=Td)
         K.gemm(go, c["Wp"], R, dh, d, b_trans=True, act=K.AW_ACT_GELU_TANH, pre=c["h"], C=gh)
         K.gemm(go, c["g"], d, dh, R, a_trans=True, b_trans=True, C=slot(mod["c_proj"].weight), accumulate=True,
@@ -424,8 +383,8 @@ def block(mod, x):
         pa = float(at.attn_pdrop) if training else 0.0
         s_attn, s_mlp, s_probs = _seed(p), _seed(p), _seed(pa)
         xr = x.reshape(R, d).contiguous().float()
-        Wqkv, Wo = _cast(at.c_attn.weight, Td), _cast(at.c_proj.weight, Td)
-        Wfc, Wp = _cast(mlp.c_fc.weight, Td), _cast(mlp.c_proj.weight, Td)
+        Wqkv, Wo = cast(at.c_attn.weight, Td), cast(at.c_proj.weight, Td)
+        Wfc, Wp = cast(mlp.c_fc.weight, Td), cast(mlp.c_proj.weight, Td)
         a, mu1, rs1 = e(R, d, dt=Td), e(R), e(R)
         K.layernorm_fwd(xr, mod.ln_1.weight, mod.ln_1.bias, mod.ln_1.eps, a, mu1, rs1)
         qkv = e(R, 3 * d, dt=Td)
@@ -455,7 +414,7 @@ def block(mod, x):
         p, pa = sv.p, sv.pa
         s_attn, s_mlp, s_probs = sv.seeds
         gx = g.reshape(R, d).float().clone()     # residual-stream gradient; the LayerNorm backwards add into it
-        go = _masked_copy(gx, Td, p, s_mlp)
+        go = _operand_copy(gx, Td, 3, (p, s_mlp))
         # ---- MLP
         gh = e(R, 4 * d, dt=Td)
         K.gemm(go, c["Wp"], R, 4 * d, d, b_trans=True, act=K.AW_ACT_GELU_TANH, pre=c["h"], C=gh)

@@ -90,6 +90,16 @@ class Geometry:
                                                         a_rowsum=gb, **self.wgrad))
 
 
+def biases(convs):
+    """``forward``'s biases of a stack given as its (conv1, conv2) module pairs."""
+    return [(c1.bias, c2.bias) for c1, c2 in convs]
+
+
+def grads(convs, slot):
+    """``backward``'s grads(r, i) of the same pairs: the accumulators of block r's conv i (weight, then bias)."""
+    return lambda r, i: (slot(convs[r][i].weight), slot(convs[r][i].bias))
+
+
 class Saved:
     """What one stack forward leaves for its backward.  geo: the stack's Geometry; route: "chain", "conv" or "bn".
     xs[r] / a0s[r]: block r's input and its GELU operand copy, hs[r] / a1s[r]: conv1's pre-activation and its GELU --

@@ -20,24 +20,19 @@ weight-gradient GEMMs with the bias gradient fused as an A-row-sum).  Operands a
 from __future__ import annotations
 
 import os
+import types
 import weakref
 
 import torch
 
 from . import _native as nat
+from . import boundary
 from . import kernels as K
 from . import operands
 from . import resstack
 from .precision import operand_dtype  # noqa: F401  (re-exported: model/ and arcweld.decoder import it from here)
 
 F32 = torch.float32
-
-
-def _mix(seed: int, salt: int) -> int:
-    z = (seed * 0x9E3779B97F4A7C15 + salt * 0xBF58476D1CE4E5B9 + 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
-    z ^= z >> 31
-    z = (z * 0xD6E8FEB86659FD93) & 0xFFFFFFFFFFFFFFFF
-    return z ^ (z >> 32)
 
 
 def rng_snapshot(m, dev, p_drop, zero=None):
@@ -121,6 +116,53 @@ def _params(m):
                 dec0=m.decoder[0], dec=dec, t1=rp[0], bn=rp[1], t2=rp[3], enc_bn=enc_bn, dec_bn=dec_bn)
 
 
+def routes(m, sh, T):
+    """The launch routes of a pass over `m` with operand dtype T: ``forward`` reads all, ``decode`` the decoder's."""
+    H, D, R, k1 = sh.H, sh.D, sh.R, sh.k1
+    rt = types.SimpleNamespace(RT=resid_dtype(m, T))
+    # bf16: a whole ResBlock stack as ONE persistent launch (csrc/reschain.hip), the same tensors bit for bit
+    rt.enc_chain = K.res_chain_ok(H, R, T, rt.RT) and not m.batch_norm
+    rt.dec_chain = K.res_chain_ok(H, R, T, rt.RT, 3, sh.S, "DEC") and not m.batch_norm
+    # With the encoder chain and the reference's patch 25 (32 padded columns) patchify and the patch-embed GEMM run as
+    # the head of the chain launch, which writes patches, x0 and a0 itself (ARCWELD_CHAIN_HEAD=0: two launches)
+    rt.enc_head = rt.enc_chain and sh.ldp == 32 and K.chain_head_ok()
+    # The sep conv (D = 64) rides as the tail of the encoder chain launch when that runs: x_R is still in LDS there,
+    # so z costs 16 more K steps on a quarter of the fragments and no launch of its own (ARCWELD_SEP_TAIL=0: a GEMM)
+    rt.sep_tail = rt.enc_chain and D == 64 and K.sep_tail_ok()
+    # In the bf16 operand mode the ConvT output Y is bf16 (what autocast keeps for a ConvTranspose1d output; the BN
+    # statistics still come from the f32 values in the epilogue): half the bytes of the GEMM's output and of the head's
+    # passes over Y.  Round 3 measured it even over the step (the head passes are VALU-bound); on the round-4 step it
+    # measured 3.162 / 3.155 / 3.157 vs 3.170 / 3.170 / 3.193 ms for an f32 Y (alternating, same box).
+    # ARCWELD_HEAD_BF16=0 keeps Y in f32.
+    rt.bf_y = T != F32 and K.head_bf16_ok(H) and os.environ.get("ARCWELD_HEAD_BF16", "1") == "1"
+    # The un-patch ConvT rides as the tail of the decoder chain launch when that runs and Y is bf16: x_R is still in
+    # LDS there, so the ConvT is k1 more 1-tap convs and no launch of its own (ARCWELD_CONVT_TAIL=0: a GEMM)
+    rt.convt_tail = rt.dec_chain and rt.bf_y and k1 <= nat.RES_TAIL_MAX and K.convt_tail_ok()
+    # ... and the 1x1 conv (D = 64) as its head: the launch loads its rows of zq_T and writes y0 / ya0 itself
+    # (ARCWELD_CHAIN_HEAD=0: a GEMM)
+    rt.dec_head = rt.dec_chain and D == 64 and K.chain_head_ok()
+    return rt
+
+
+def _decoder_walk(m, pr, ops, rt, T, y0, ya0, x_hat, stack, **unpatch):
+    """Decoder ResBlocks from y0 / ya0 = GELU(y0), the un-patch ConvT, the BatchNorm statistics and the fused head
+    into x_hat, on the routes rt.  stack: resstack.forward's keywords, unpatch: boundary.unpatch_fwd's.  Returns
+    (the ConvT's input operand, Y as (N k1, H), the BatchNorm stats, the saved stack)."""
+    sh = VQVAEShapes(m, 1)
+    H, R, k1, N = sh.H, sh.R, sh.k1, ya0.shape[0]
+    Wt1, t1 = ops["Wt1"], pr["t1"]
+    Y = torch.empty(N, k1 * H, device=ya0.device, dtype=T if rt.bf_y else F32)
+    _, yR_T, rec = resstack.forward(resstack.Geometry(3, H, sh.S), y0, ya0,
+                                    [(ops[f"dec{r}_1"], ops[f"dec{r}_2"]) for r in range(R)],
+                                    resstack.biases(pr["dec"]), pr["dec_bn"], T=T, RT=rt.RT, chain=rt.dec_chain,
+                                    tail=(Wt1, t1.bias, Y, unpatch.get("colstats")) if rt.convt_tail else None,
+                                    **stack)
+    if R == 0:
+        yR_T = boundary.operand(y0, T)
+    stats = boundary.unpatch_fwd(yR_T, Wt1, t1, pr["bn"], pr["t2"], Y, sh.Q, x_hat, convt=not rt.convt_tail, **unpatch)
+    return yR_T, Y.view(N * k1, H), stats, rec
+
+
 class Saved:
     pass
 
@@ -179,10 +221,10 @@ def forward(m, x, training: bool, need_backward: bool, dtype=None, seed: int = 0
     e = lambda *s, dt=F32: torch.empty(*s, device=dev, dtype=dt)  # noqa: E731
     sv = Saved()
     sv.sh, sv.T, sv.p_drop, sv.training = sh, T, p_drop, training
-    RT = sv.RT = resid_dtype(m, T)
-    acc = accumulators(m, dev, sh.K, H, zero=False)
+    rt = routes(m, sh, T)
+    RT = sv.RT = rt.RT
+    acc = sv.acc = accumulators(m, dev, sh.K, H, zero=False)
     sv.ctr = rng_snapshot(m, dev, p_drop, zero=acc["block"])
-    sv.acc = acc
     # the head-backward sums of the block belong to one saved forward at a time: the owner is held by a weak
     # reference, released by its backward -- or by its collection when it is never backpropagated
     owner = m.__dict__.get("_acc_owner")
@@ -193,43 +235,32 @@ def forward(m, x, training: bool, need_backward: bool, dtype=None, seed: int = 0
 
     # ---- operand copies of the weights (relayout + cast): persistent, refreshed by one batched relayout only when
     #      a weight changed outside the optimizer (the flat RAdam rewrites them in its update kernel)
-    ops = operands.get(m, ("vqvae", T), lambda: _operand_jobs(m, T))
-    Wp, Ws, Wd0, Wt1 = ops["Wp"], ops["Ws"], ops["Wd0"], ops["Wt1"]
-    enc_w = [(ops[f"enc{r}_1"], ops[f"enc{r}_2"]) for r in range(R)]
-    dec_w = [(ops[f"dec{r}_1"], ops[f"dec{r}_2"]) for r in range(R)]
-    sv.ops = ops
+    ops = sv.ops = operands.get(m, ("vqvae", T), lambda: _operand_jobs(m, T))
+    Wp, Ws, Wd0 = ops["Wp"], ops["Ws"], ops["Wd0"]
 
-    # ---- patch embed.  With the encoder chain and the reference's patch 25 (32 padded columns) patchify and the GEMM
-    #      run as the head of the chain launch, which writes patches, x0 and a0 itself (ARCWELD_CHAIN_HEAD=0: these
-    #      two launches)
-    enc_chain = K.res_chain_ok(H, R, T, RT) and pr["enc_bn"] is None
-    enc_head = enc_chain and sh.ldp == 32 and K.chain_head_ok()
+    # ---- patch embed (unless it runs as the head of the encoder chain launch)
     patches = e(N, sh.ldp, dt=T)
     x0, a0 = e(N, H, dt=RT), e(N, H, dt=T)
-    if not enc_head:
+    if not rt.enc_head:
         K.patchify(x, P, patches)
-        K.gemm(patches, Wp, N, H, sh.ldp, bias=pr["pe"].bias, C=x0, C2=a0, c2_mode=1, flops=2 * N * H * P)
+        boundary.conv_fwd(patches, Wp, pr["pe"].bias, x0, C2=a0, c2_mode=1, flops=2 * N * H * P)
 
-    # ---- encoder ResBlocks (per-token: centre taps).  bf16: the whole stack as ONE persistent launch
-    #      (csrc/reschain.hip), the same tensors bit for bit; the last block writes only the operand copy of x_R (all
-    #      the sep conv consumes)
-    stack = dict(T=T, RT=RT, p_drop=p_drop, ctr=sv.ctr, training=training, save=need_backward)
-    # The sep conv (D = 64) rides as the tail of the encoder chain launch when that runs: x_R is still in LDS there,
-    # so z costs 16 more K steps on a quarter of the fragments and no launch of its own (ARCWELD_SEP_TAIL=0: the GEMM
-    # below)
+    # ---- encoder ResBlocks (per-token: centre taps); the last block writes only the operand copy of x_R (all the
+    #      sep conv consumes)
+    stack = dict(p_drop=p_drop, ctr=sv.ctr, training=training, save=need_backward)
     z = e(N, D)
-    sep_tail = enc_chain and D == 64 and K.sep_tail_ok()
-    _, xR_T, sv.enc = resstack.forward(resstack.Geometry(1, H, S), x0, a0, enc_w, _biases(pr["enc"]), pr["enc_bn"],
-                                       seeds=[_mix(seed, 100 + r) for r in range(R)],
-                                       chain=enc_chain,
-                                       sep=(Ws, pr["sep"].bias, z) if sep_tail else None,
-                                       head=(x, Wp, pr["pe"].bias, patches, P) if enc_head else None, **stack)
+    _, xR_T, sv.enc = resstack.forward(resstack.Geometry(1, H, S), x0, a0,
+                                       [(ops[f"enc{r}_1"], ops[f"enc{r}_2"]) for r in range(R)],
+                                       resstack.biases(pr["enc"]), pr["enc_bn"], T=T, RT=RT,
+                                       seeds=[boundary.mix(seed, 100 + r) for r in range(R)], chain=rt.enc_chain,
+                                       sep=(Ws, pr["sep"].bias, z) if rt.sep_tail else None,
+                                       head=(x, Wp, pr["pe"].bias, patches, P) if rt.enc_head else None, **stack)
     if R == 0:
-        xR_T = _operand(x0, T)
+        xR_T = boundary.operand(x0, T)
 
-    # ---- SepCNNBlock -> z (B, S, D)
-    if not sep_tail:
-        K.gemm(xR_T, Ws, N, D, H, bias=pr["sep"].bias, C=z)
+    # ---- SepCNNBlock -> z (B, S, D) (unless it ran as the tail of the encoder chain launch)
+    if not rt.sep_tail:
+        boundary.conv_fwd(xR_T, Ws, pr["sep"].bias, z)
 
     # ---- vector quantizer
     Kc = sh.K
@@ -250,53 +281,25 @@ def forward(m, x, training: bool, need_backward: bool, dtype=None, seed: int = 0
         K.vq_finalize(counts, sq, N, Kc, D, m.vector_quantization.beta, emb_loss, perplexity,
                       count_groups=VQ_COUNT_GROUPS)
     if pr["E"] is None or T == F32:
-        zq_T = zq if T == F32 else _cast(zq, T)
+        zq_T = zq if T == F32 else boundary.cast(zq, T)
 
-    # ---- decoder: 1x1 conv + ResBlocks with k=3 convs along the window
+    # ---- decoder: 1x1 conv (unless it runs as the head of the decoder chain launch), ResBlocks with k=3 convs along
+    #      the window, un-patch ConvT(H->H, k1) with BN statistics in the epilogue, then the fused head
     y0, ya0 = e(N, H, dt=RT), e(N, H, dt=T)
-    # In the bf16 operand mode the ConvT output Y is bf16 (what autocast keeps for a ConvTranspose1d output; the BN
-    # statistics still come from the f32 values in the epilogue): half the bytes of the GEMM's output and of the head's
-    # passes over Y.  Round 3 measured it even over the step (the head passes are VALU-bound); on the round-4 step it
-    # measured 3.162 / 3.155 / 3.157 vs 3.170 / 3.170 / 3.193 ms for an f32 Y (alternating, same box).
-    # ARCWELD_HEAD_BF16=0 keeps Y in f32.
-    bf_y = T != F32 and K.head_bf16_ok(H) and os.environ.get("ARCWELD_HEAD_BF16", "1") == "1"
-    Y = e(N, k1 * H, dt=T if bf_y else F32)
-    colstats = acc["colstats"] if training else None
-    # The un-patch ConvT rides as the tail of the decoder chain launch when that runs and Y is bf16: x_R is still in
-    # LDS there, so the ConvT is k1 more 1-tap convs and no launch of its own (ARCWELD_CONVT_TAIL=0: the GEMM below)
-    dec_chain = K.res_chain_ok(H, R, T, RT, 3, S, "DEC") and pr["dec_bn"] is None
-    convt_tail = dec_chain and bf_y and k1 <= nat.RES_TAIL_MAX and K.convt_tail_ok()
-    # ... and the 1x1 conv (D = 64) as its head: the launch loads its rows of zq_T and writes y0 / ya0 itself
-    # (ARCWELD_CHAIN_HEAD=0: the GEMM below)
-    dec_head = dec_chain and D == 64 and K.chain_head_ok()
-    if not dec_head:
-        K.gemm(zq_T, Wd0, N, H, D, bias=pr["dec0"].bias, C=y0, C2=ya0, c2_mode=1)
-    _, yR_T, sv.dec = resstack.forward(resstack.Geometry(3, H, S), y0, ya0, dec_w, _biases(pr["dec"]), pr["dec_bn"],
-                                       seeds=[_mix(seed, 200 + r) for r in range(R)], chain=dec_chain,
-                                       tail=(Wt1, pr["t1"].bias, Y, colstats) if convt_tail else None,
-                                       head=(zq_T, Wd0, pr["dec0"].bias) if dec_head else None, **stack)
-    if R == 0:
-        yR_T = _operand(y0, T)
-
-    # ---- un-patch: ConvT(H->H, k1) with BN statistics in the epilogue, then the fused head
-    bn = pr["bn"]
-    if not convt_tail:
-        K.gemm(yR_T, Wt1, N, k1 * H, H, bias=pr["t1"].bias, bias_mod=H, C=Y, colstats=colstats, stats_mod=H)
-    stats = e(4 * H)
-    K.bn_finalize(colstats, N * k1, H, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                  bn.num_batches_tracked if training else None, bn.eps,
-                  bn.momentum if bn.momentum is not None else 0.1, training, stats)
+    if not rt.dec_head:
+        boundary.conv_fwd(zq_T, Wd0, pr["dec0"].bias, y0, C2=ya0, c2_mode=1)
     x_hat = e(sh.B, sh.L, sh.C)
-    Y2 = Y.view(N * k1, H)
     sv.head_fused = not head and need_backward and fused_head_ok(H)
-    if not sv.head_fused:
-        K.unpatch_head_fwd(Y2, sh.Q, stats, pr["t2"].weight.view(H, 5), pr["t2"].bias, x_hat)
+    stack.update(seeds=[boundary.mix(seed, 200 + r) for r in range(R)],
+                 head=(zq_T, Wd0, pr["dec0"].bias) if rt.dec_head else None)
+    yR_T, Y2, stats, sv.dec = _decoder_walk(m, pr, ops, rt, T, y0, ya0, x_hat, stack, training=training,
+                                            colstats=acc["colstats"] if training else None, stats_mod=H,
+                                            head=not sv.head_fused)
 
     if not need_backward:
         return emb_loss, x_hat, perplexity, idx, None
-    sv.patches, sv.xR_T, sv.z, sv.idx, sv.zq_T, sv.yR_T = patches, xR_T, z, idx, zq_T, yR_T
-    sv.Y2, sv.stats = Y2, stats
-    sv.Ws, sv.Wd0, sv.Wt1 = Ws, Wd0, Wt1
+    sv.patches, sv.xR_T, sv.z, sv.idx, sv.zq_T = patches, xR_T, z, idx, zq_T
+    sv.yR_T, sv.Y2, sv.stats = yR_T, Y2, stats
     return emb_loss, x_hat, perplexity, idx, sv
 
 
@@ -343,7 +346,7 @@ def encode(m, x, dtype=F32):
     patches = e(N, sh.ldp, dt=T)
     K.patchify(x, P, patches)
     xr, a = e(N, H), e(N, H, dt=T)
-    K.gemm(patches, Wp, N, H, sh.ldp, bias=pr["pe"].bias, C=xr, C2=a, c2_mode=1, flops=2 * N * H * P)
+    boundary.conv_fwd(patches, Wp, pr["pe"].bias, xr, C2=a, c2_mode=1, flops=2 * N * H * P)
     ew = [(e(H, H, dt=T), e(H, H, dt=T)) for _ in range(R)]
     Ws = e(D, H, dt=T)
     geo = resstack.Geometry(1, H, sh.S)
@@ -351,12 +354,12 @@ def encode(m, x, dtype=F32):
                             + [(pr["sep"].weight, D, H, 1, 0, 0, Ws)])
     # x <- x + conv2(gelu(h)) in place (row-local epilogue), a <- gelu(x); the sep conv consumes x_R itself (no GELU),
     # written in the operand dtype.  BatchNorm ResBlocks: the module mode decides batch vs running statistics
-    _, xR_T, _ = resstack.forward(geo, xr, a, ew, _biases(pr["enc"]), pr["enc_bn"], T=T, RT=F32, training=m.training,
-                                  in_place=True, save=False)
+    _, xR_T, _ = resstack.forward(geo, xr, a, ew, resstack.biases(pr["enc"]), pr["enc_bn"], T=T, RT=F32,
+                                  training=m.training, in_place=True, save=False)
     if R == 0:
-        xR_T = _operand(xr, T)
+        xR_T = boundary.operand(xr, T)
     z = e(N, D)
-    K.gemm(xR_T, Ws, N, D, H, bias=pr["sep"].bias, C=z)
+    boundary.conv_fwd(xR_T, Ws, pr["sep"].bias, z)
     if pr["E"] is None:   # residual VQ: eval-mode assignment (no EMA), one token per position needs nq == 1
         rvq = m.vector_quantization.vq
         if rvq.num_quantizers != 1:
@@ -389,7 +392,7 @@ def decode(m, idx, dtype=None):
     if idx.dtype != torch.int64 or idx.dim() != 1:
         raise ValueError("decode expects a flat int64 tensor of W*S codebook indices")
     sh = VQVAEShapes(m, 1)
-    H, D, S, R, k1, Kc = sh.H, sh.D, sh.S, sh.R, sh.k1, sh.K
+    H, D, S, Kc = sh.H, sh.D, sh.S, sh.K
     N = idx.numel()
     if N == 0 or N % S:
         raise ValueError(f"decode: {N} ids are not a positive multiple of the {S} ids of one window")
@@ -398,68 +401,30 @@ def decode(m, idx, dtype=None):
     pr = _params(m)
     dev = idx.device
     e = lambda *s, dt=F32: torch.empty(*s, device=dev, dtype=dt)  # noqa: E731
-    RT = resid_dtype(m, T)
+    rt = routes(m, sh, T)
     ops = operands.get(m, ("vqvae", T), lambda: _operand_jobs(m, T))
-    Wd0, Wt1 = ops["Wd0"], ops["Wt1"]
-    dec_w = [(ops[f"dec{r}_1"], ops[f"dec{r}_2"]) for r in range(R)]
+    Wd0, b0 = ops["Wd0"], pr["dec0"].bias
 
     # ---- decoder 1x1 conv: over the codebook + a two-table gather, or (K > N) a codebook gather + the GEMM
     bad = torch.zeros(1, device=dev, dtype=torch.int32)
-    y0, ya0 = e(N, H, dt=RT), e(N, H, dt=T)
+    y0, ya0 = e(N, H, dt=rt.RT), e(N, H, dt=T)
     E = pr["E"]
     if Kc <= N:
-        table_x, table_a = e(Kc, H, dt=RT), e(Kc, H, dt=T)
-        K.gemm(_operand(E, T), Wd0, Kc, H, D, bias=pr["dec0"].bias, C=table_x, C2=table_a, c2_mode=1)
+        table_x, table_a = e(Kc, H, dt=rt.RT), e(Kc, H, dt=T)
+        boundary.conv_fwd(boundary.operand(E, T), Wd0, b0, table_x, C2=table_a, c2_mode=1)
         K.vq_decode_gather(idx, table_x, table_a, y0, ya0, bad)
     else:
         zq = e(N, D)
         K.vq_decode_gather(idx, E, None, zq, None, bad)
-        K.gemm(_operand(zq, T), Wd0, N, H, D, bias=pr["dec0"].bias, C=y0, C2=ya0, c2_mode=1)
+        boundary.conv_fwd(boundary.operand(zq, T), Wd0, b0, y0, C2=ya0, c2_mode=1)
 
-    # ---- decoder ResBlocks + un-patch ConvT, on the routes forward() takes (chain, ConvT tail)
-    bf_y = T != F32 and K.head_bf16_ok(H) and os.environ.get("ARCWELD_HEAD_BF16", "1") == "1"
-    Y = e(N, k1 * H, dt=T if bf_y else F32)
-    dec_chain = K.res_chain_ok(H, R, T, RT, 3, S, "DEC") and pr["dec_bn"] is None
-    convt_tail = dec_chain and bf_y and k1 <= nat.RES_TAIL_MAX and K.convt_tail_ok()
-    _, yR_T, _ = resstack.forward(resstack.Geometry(3, H, S), y0, ya0, dec_w, _biases(pr["dec"]), pr["dec_bn"],
-                                  T=T, RT=RT, training=m.training, chain=dec_chain, save=False,
-                                  tail=(Wt1, pr["t1"].bias, Y, None) if convt_tail else None)
-    if R == 0:
-        yR_T = _operand(y0, T)
-    if not convt_tail:
-        K.gemm(yR_T, Wt1, N, k1 * H, H, bias=pr["t1"].bias, bias_mod=H, C=Y)
-
-    # ---- head on the running statistics
-    bn = pr["bn"]
-    stats = e(4 * H)
-    K.bn_finalize(None, N * k1, H, bn.weight, bn.bias, bn.running_mean, bn.running_var, None, bn.eps,
-                  bn.momentum if bn.momentum is not None else 0.1, False, stats)
+    # ---- decoder ResBlocks, un-patch ConvT and the head on the running statistics: forward()'s walk and routes
     x_hat = e(W, sh.L, sh.C)
-    K.unpatch_head_fwd(Y.view(N * k1, H), sh.Q, stats, pr["t2"].weight.view(H, 5), pr["t2"].bias, x_hat)
+    _decoder_walk(m, pr, ops, rt, T, y0, ya0, x_hat, dict(training=m.training, save=False), training=False)
     nbad = int(bad.item())
     if nbad:
         raise ValueError(f"decode: {nbad} of {N} ids lie outside the codebook [0, {Kc})")
     return x_hat
-
-
-def _cast(t, T):
-    out = torch.empty(t.shape, device=t.device, dtype=T)
-    K.cast(t, out)
-    return out
-
-
-def _operand(x, T):
-    """x in the operand dtype (what a stack of no blocks hands to the next conv)."""
-    return x if x.dtype == T else _cast(x, T)
-
-
-def _biases(convs):
-    return [(c1.bias, c2.bias) for c1, c2 in convs]
-
-
-def _grads(convs, slot):
-    """resstack.backward's grads(r, i): the accumulators of block r's conv i (weight, then bias)."""
-    return lambda r, i: (slot(convs[r][i].weight), slot(convs[r][i].bias))
 
 
 @K.store_policy(nat.AW_STORE_WT)
@@ -468,48 +433,38 @@ def backward(m, sv, g_emb, g_xhat, slot, mid_hook=None):
 
     ``mid_hook()`` runs once the decoder side is done (head, ConvT, decoder ResBlocks, decoder 1x1, codebook): those
     gradients are final there, which lets a data-parallel step reduce them while the encoder backward runs."""
-    sh, T, p_drop = sv.sh, sv.T, sv.p_drop
-    H, D, N, S, R, P, k1 = sh.H, sh.D, sh.N, sh.S, sh.R, sh.P, sh.k1
+    sh, T, RT, p_drop, ops = sv.sh, sv.T, sv.RT, sv.p_drop, sv.ops
+    H, D, N, R, P = sh.H, sh.D, sh.N, sh.R, sh.P
     pr = _params(m)
     dev = g_xhat.device
     e = lambda *s, dt=F32: torch.empty(*s, device=dev, dtype=dt)  # noqa: E731
     g_xhat = g_xhat.contiguous()
-    bn = pr["bn"]
+    bnm = m.batch_norm and R > 0    # BatchNorm ResBlocks: each block applies its own dropout mask to the gradient
 
-    # ---- head + BN backward
-    gsums = sv.head_gsums
+    def into_stack(rec, copy):    # epilogue of the GEMM in front of a stack's backward: + the masked operand copy
+        return dict(C2=None if bnm else copy, c2_mode=0 if bnm else (3 if R > 0 else 2),
+                    drop2=(p_drop, rec.seeds[-1] if R > 0 else 0), seed_ptr=sv.ctr)
+
+    # ---- head + BN backward, ConvT1 weight gradient and input gradient -> grad of the decoder output
     owner = m.__dict__.get("_acc_owner")
     if owner is not None and owner() is sv:
         m.__dict__["_acc_owner"] = None
-    if not getattr(sv, "head_pass1_done", False):
-        K.unpatch_head_bwd1(sv.Y2, sh.Q, sv.stats, pr["t2"].weight.view(H, 5), g_xhat, gsums,
-                            slot(pr["t2"].weight).view(H, 5), slot(pr["t2"].bias), slot(bn.weight), slot(bn.bias))
-    gY = e(N * k1, H, dt=T)
-    K.unpatch_head_bwd2(sv.Y2, sh.Q, sv.stats, pr["t2"].weight.view(H, 5), g_xhat, gsums, sv.training, gY,
-                        slot(pr["t1"].bias))
-    gY2 = gY.view(N, k1 * H)
-    # ConvT1 weight gradient, computed as [i][(j,o)] and accumulated straight into the (H_in, H_out, k1) layout
-    K.gemm(sv.yR_T, gY2, H, k1 * H, N, a_trans=True, b_trans=True, C=slot(pr["t1"].weight).view(H, H * k1),
-           accumulate=True, col_map=(H, k1, 0))
-    # ConvT1 input gradient -> grad of the decoder output, plus the dropout-masked operand for its last block
-    RT = sv.RT
     gy, go = e(N, H, dt=RT), e(N, H, dt=T)
-    bnm = m.batch_norm and R > 0    # BatchNorm ResBlocks: each block applies its own dropout mask to gy
-    K.gemm(gY2, sv.Wt1, N, H, k1 * H, b_trans=True, C=gy, C2=None if bnm else go, c2_mode=0 if bnm else
-           (3 if R > 0 else 2), drop2=(p_drop, sv.dec.seeds[-1] if R > 0 else 0), seed_ptr=sv.ctr)
+    boundary.unpatch_bwd(sv.yR_T, ops["Wt1"], pr["t1"], pr["bn"], pr["t2"], sv.Y2, sh.Q, sv.stats, g_xhat, sv.head_gsums,
+                         slot, T, training=sv.training, pass1=not getattr(sv, "head_pass1_done", False), gx=gy,
+                         **into_stack(sv.dec, go))
 
     # ---- decoder ResBlocks (reverse; bf16: the input-gradient chain of all R blocks in one launch).  The weight
     #      gradients of the whole stack are deferred and issued as ONE grouped launch (every tile runs the full token
     #      reduction: no split-K, no slab reduce); their operands stay alive until then
-    dgw = [(sv.ops[f"dgw{r}_1"], sv.ops[f"dgw{r}_2"]) for r in range(R)]
-    gy, go, wgrads = resstack.backward(sv.dec, gy, go, dgw, _grads(pr["dec"], slot), pr["dec_bn"], slot)
+    dgw = [(ops[f"dgw{r}_1"], ops[f"dgw{r}_2"]) for r in range(R)]
+    gy, go, wgrads = resstack.backward(sv.dec, gy, go, dgw, resstack.grads(pr["dec"], slot), pr["dec_bn"], slot)
     K.gemm_grouped(wgrads)
 
     # ---- decoder 1x1 conv (weight (H, D, 1) is a contiguous [H][D] matrix)
-    K.gemm(go, sv.zq_T, H, D, N, a_trans=True, b_trans=True, C=slot(pr["dec0"].weight).view(H, D), accumulate=True,
-           a_rowsum=slot(pr["dec0"].bias))
+    boundary.conv_wgrad(go, sv.zq_T, slot(pr["dec0"].weight).view(H, D), slot(pr["dec0"].bias))
     gzq = e(N, D)
-    K.gemm(go, sv.Wd0, N, D, H, b_trans=True, C=gzq)
+    boundary.conv_dgrad(go, ops["Wd0"], gzq)
 
     # ---- vector quantizer (straight-through + codebook/commitment loss)
     dz = e(N, D)
@@ -526,22 +481,20 @@ def backward(m, sv, g_emb, g_xhat, slot, mid_hook=None):
         with K.store_policy(nat.AW_STORE_NT):     # the hook's own launches (e.g. collectives) keep the default policy
             mid_hook()
     if dz_T is None:
-        dz_T = _cast(dz, T)
+        dz_T = boundary.cast(dz, T)
 
     # ---- SepCNNBlock
-    K.gemm(dz_T, sv.xR_T, D, H, N, a_trans=True, b_trans=True, C=slot(pr["sep"].weight).view(D, H), accumulate=True,
-           a_rowsum=slot(pr["sep"].bias))
+    boundary.conv_wgrad(dz_T, sv.xR_T, slot(pr["sep"].weight).view(D, H), slot(pr["sep"].bias))
     gx, gxo = e(N, H, dt=RT), e(N, H, dt=T)
-    K.gemm(dz_T, sv.Ws, N, H, D, b_trans=True, C=gx, C2=None if bnm else gxo, c2_mode=0 if bnm else
-           (3 if R > 0 else 2), drop2=(p_drop, sv.enc.seeds[-1] if R > 0 else 0), seed_ptr=sv.ctr)
+    boundary.conv_dgrad(dz_T, ops["Ws"], gx, **into_stack(sv.enc, gxo))
 
     # ---- encoder ResBlocks (reverse), on the forward's operand copies; weight gradients deferred as in the decoder
-    gx, gxo, wgrads = resstack.backward(sv.enc, gx, gxo, sv.enc.ws, _grads(pr["enc"], slot), pr["enc_bn"], slot)
+    gx, gxo, wgrads = resstack.backward(sv.enc, gx, gxo, sv.enc.ws, resstack.grads(pr["enc"], slot), pr["enc_bn"],
+                                        slot)
     K.wgrad_issue(wgrads)      # the 16 per-token conv weight gradients: one stream-K batch (bf16) or one grouped launch
 
     # ---- patch embed weight/bias
-    K.gemm(gxo, sv.patches, H, P, N, a_trans=True, b_trans=True, C=slot(pr["pe"].weight).view(H, P),
-           accumulate=True, a_rowsum=slot(pr["pe"].bias))
+    boundary.conv_wgrad(gxo, sv.patches, slot(pr["pe"].weight).view(H, P), slot(pr["pe"].bias))
 
 
 class VQVAEPatchFunction(torch.autograd.Function):
