@@ -485,12 +485,32 @@ def res_pack_weights(src, fwd=None, bwd=None, taps=1, stream=None, job_taps=None
 
 
 # ------------------------------------------------------------------------------------------------ VQ
+def _chk_vq(who, name, t, shape, dtypes=(torch.float32,)):
+    """The VQ entry points take raw pointers and sizes: a transposed, sliced or wrongly typed tensor would be read or
+    written as garbage in silence."""
+    if t.dtype not in dtypes or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        want = " or ".join(str(d).replace("torch.", "") for d in dtypes)
+        raise nat.NativeError(f"{who}: {name} must be a contiguous {want} tensor of shape {tuple(shape)} (got "
+                              f"{str(t.dtype).replace('torch.', '')} {tuple(t.shape)}, strides {tuple(t.stride())})")
+
+
 def vq_forward(z2d, E, zq, idx, counts, sqerr, stream=None, zq_copy=None, count_groups=1):
     """zq_copy: optional bf16/f32 tensor that also receives z_q.  count_groups > 1: counts holds that many partial
     histograms of K floats (aw_vq_forward_ex2; vq_finalize sums them)."""
+    if z2d.dim() != 2 or E.dim() != 2:
+        raise nat.NativeError(f"vq_forward: z must be (N, D) and E (K, D) (got {tuple(z2d.shape)}, {tuple(E.shape)})")
     N, D = z2d.shape
     Kc = E.shape[0]
-    assert counts.numel() >= count_groups * Kc, "counts: count_groups x K floats"
+    _chk_vq("vq_forward", "z", z2d, (N, D))
+    _chk_vq("vq_forward", "E", E, (Kc, D))
+    _chk_vq("vq_forward", "zq", zq, (N, D))
+    _chk_vq("vq_forward", "idx", idx, (N,), (torch.int64,))
+    _chk_vq("vq_forward", "sqerr", sqerr, (1,), (torch.float64,))
+    if zq_copy is not None:
+        _chk_vq("vq_forward", "zq_copy", zq_copy, (N, D), (torch.float32, torch.bfloat16))
+    if counts.dtype != torch.float32 or not counts.is_contiguous() or counts.numel() < count_groups * Kc:
+        raise nat.NativeError(f"vq_forward: counts must hold count_groups x K = {count_groups} x {Kc} contiguous "
+                              f"float32 values (got {str(counts.dtype).replace('torch.', '')} {tuple(counts.shape)})")
     _maybe_timed(stream, "vq_fwd", 2.0 * N * Kc * D, lambda sp: call(
         "aw_vq_forward_ex2", ptr(z2d), ptr(E), N, Kc, D, ptr(zq), ptr(idx), ptr(counts), int(count_groups),
         ptr(sqerr), ptr(zq_copy), dtype_code(zq_copy.dtype) if zq_copy is not None else 0, sp),
@@ -506,7 +526,20 @@ def vq_finalize(counts, sqerr, N, K, D, beta, loss, perplexity, stream=None, cou
 
 def vq_backward(z2d, E, idx, g_zq, g_loss, beta, dz, dE, stream=None, dz_copy=None):
     """dz_copy: optional bf16/f32 tensor that also receives dz (aw_vq_backward_ex)."""
+    if z2d.dim() != 2 or E.dim() != 2:
+        raise nat.NativeError(f"vq_backward: z must be (N, D) and E (K, D) (got {tuple(z2d.shape)}, {tuple(E.shape)})")
     N, D = z2d.shape
+    _chk_vq("vq_backward", "z", z2d, (N, D))
+    _chk_vq("vq_backward", "E", E, (E.shape[0], D))
+    _chk_vq("vq_backward", "idx", idx, (N,), (torch.int64,))
+    if g_zq is not None:
+        _chk_vq("vq_backward", "g_zq", g_zq, (N, D))
+    if g_loss is not None and (g_loss.dtype != torch.float32 or g_loss.numel() != 1):
+        raise nat.NativeError("vq_backward: g_loss must be one float32 on the device")
+    _chk_vq("vq_backward", "dz", dz, (N, D))
+    _chk_vq("vq_backward", "dE", dE, (E.shape[0], D))
+    if dz_copy is not None:
+        _chk_vq("vq_backward", "dz_copy", dz_copy, (N, D), (torch.float32, torch.bfloat16))
     if dz_copy is None:
         call("aw_vq_backward", ptr(z2d), ptr(E), ptr(idx), ptr(g_zq), ptr(g_loss), N, E.shape[0], D, float(beta),
              ptr(dz), ptr(dE), stream_ptr(stream))
