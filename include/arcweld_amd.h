@@ -460,6 +460,8 @@ int aw_mse_finalize_add(const double* sqerr, int64_t numel, const float* addend,
  * are skipped (grad None: model/transformer_decoder.py heads under find_unused_parameters).  The buffers are 16-B
  * aligned, total % 4 == 0 and every segment starts 16-B aligned; the padding after a segment (up to the next
  * multiple of 4 elements) must be zero in all four buffers and stays zero (same for aw_grad_norm_clip's grad).
+ * Nothing outside those float4s is read or written: the elements before the first segment, the gaps between
+ * segments and inactive segments may hold anything.
  * scalars come from host (step count, lr, betas, eps); `gscale` is a device scalar multiplying the gradient
  * first (clip coefficient; NULL = 1). */
 int aw_radam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, const int64_t* seg_off,

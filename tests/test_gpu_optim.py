@@ -52,13 +52,9 @@ def test_inactive_segments_untouched():
     assert not torch.equal(params[0].detach(), before[0]) and not torch.equal(params[2].detach(), before[2])
 
 
-def test_centre_tap_layout_matches_dense_layout():
-    """declare_centre_tap: (O, I, 3) weights become tap-major strided views, their dead side taps leave the
-    norm / update / all-reduce spans, and the trajectory equals the dense layout's when those taps get zero
-    gradient (the per-token encoder convs)."""
+def _centre_tap_layout_matches_dense_layout(shapes, centre):
     from arcweld.optim import RAdam
-    shapes = [(6, 5, 3), (6,), (6, 5, 3), (4, 7), (6, 5, 3)]
-    centre = [0, 2, 4]
+    oi = shapes[centre[0]][0] * shapes[centre[0]][1]
     runs = []
     for declare in (False, True):
         params = [torch.nn.Parameter(torch.tensor(gen.normal(800 + i, s, 0.3), device="cuda"))
@@ -85,7 +81,7 @@ def test_centre_tap_layout_matches_dense_layout():
         if declare:
             spans = opt.live_spans()
             covered = sum(b - a for a, b in spans)
-            assert covered < opt.flatten()[0].numel() - 2 * 3 * 30     # both dead tap blocks are outside
+            assert covered < opt.flatten()[0].numel() - 2 * 3 * oi     # both dead tap blocks are outside
             for i in centre:
                 assert torch.equal(params[i].detach()[:, :, 0], init[i][:, :, 0])
                 assert torch.equal(params[i].detach()[:, :, 2], init[i][:, :, 2])
@@ -95,6 +91,21 @@ def test_centre_tap_layout_matches_dense_layout():
     np.testing.assert_allclose(n1, n0, rtol=1e-6)
     for a, b in zip(p0, p1):
         torch.testing.assert_close(b, a, rtol=1e-6, atol=1e-7)
+
+
+def test_centre_tap_layout_matches_dense_layout():
+    """declare_centre_tap: (O, I, 3) weights become tap-major strided views, their dead side taps leave the
+    norm / update / all-reduce spans, and the trajectory equals the dense layout's when those taps get zero
+    gradient (the per-token encoder convs)."""
+    _centre_tap_layout_matches_dense_layout([(6, 5, 3), (6,), (6, 5, 3), (4, 7), (6, 5, 3)], [0, 2, 4])
+
+
+@pytest.mark.parametrize("conv", [(6, 5, 3), (6, 6, 3)])
+def test_centre_tap_layout_behind_an_ordinary_parameter(conv):
+    """The same with an ordinary parameter before the first centre-tap one, so the block starts past offset 0:
+    O*I = 30 (no multiple of 4: the block's slots are padded so every segment still starts on a float4) and
+    O*I = 36.  Every element of every centre segment must be clipped and updated as in the dense layout."""
+    _centre_tap_layout_matches_dense_layout([(6,), conv, conv, (4, 7), conv], [1, 2, 4])
 
 
 def test_state_dict_round_trip_resumes_the_trajectory():

@@ -39,7 +39,9 @@ class RAdam(torch.optim.Optimizer):
         """Conv weights (O, I, 3) whose side taps provably receive an exactly-zero gradient (a k = 3, pad = 1
         conv applied to length-1 inputs: the per-token encoder ResBlocks, model/vq_vae_patch_embedd.py:60-74,108-110).
         With weight decay 0 their side taps never change under RAdam (zero m, zero v -> zero update), so they are
-        stored tap-major in one block [3][n][O][I] and only the centre-tap block is reduced, clipped and updated.
+        stored tap-major in one block [3][n][slot], slot = O*I rounded up to a multiple of 4 elements (zero padded:
+        the update and norm kernels take float4s and need every segment to start 16-B aligned; for O*I % 4 == 0 the
+        block is [3][n][O][I] exactly), and only the centre-tap block is reduced, clipped and updated.
         The parameters become strided views (shape and values unchanged).  Call before the first flatten()."""
         if self._flat is not None:
             raise RuntimeError("declare_centre_tap must precede flatten()")
@@ -54,13 +56,11 @@ class RAdam(torch.optim.Optimizer):
             raise RuntimeError("declare_tap_major must precede flatten()")
         self._tap_major = [p for p in params]
 
-    def _build(self):
+    def _plan(self):
+        """The flat layout (no device work): which parameters keep the centre-tap / tap-major storage, the segment
+        table (param, offset, length, weight decay, group) sorted by offset, where each ordinary parameter starts,
+        the total length, and the centre-tap block's start and per-tap slot length."""
         params = [p for g in self.param_groups for p in g["params"]]
-        dev = params[0].device
-        if not all(p.device == dev and p.dtype == torch.float32 for p in params):
-            raise RuntimeError("arcweld RAdam needs all parameters as float32 on one device")
-        if dev.type != "cuda":
-            raise RuntimeError("arcweld RAdam runs on the GPU only (no CPU fallback)")
         owner_of = {id(p): gi for gi, g in enumerate(self.param_groups) for p in g["params"]}
         centre = [p for p in getattr(self, "_centre", []) if id(p) in owner_of]
         if centre and not (all(p.dim() == 3 and p.shape == centre[0].shape and p.shape[2] == 3 for p in centre)
@@ -71,28 +71,42 @@ class RAdam(torch.optim.Optimizer):
         tmaj = set(id(p) for p in getattr(self, "_tap_major", []) if id(p) in owner_of and id(p) not in cidx
                    and p.dim() == 3 and p.shape[2] == 3)
         al = lambda n: (n + 63) // 64 * 64      # 256-B aligned segments  # noqa: E731
-        # segments: (param, offset, length, weight decay, group); a centre-tap param has ONE segment (its centre)
+        # segments: (param, offset, length, weight decay, group); a centre-tap param has ONE segment (its centre).
+        # Each [O][I] matrix of the centre-tap block sits in a slot of O*I rounded up to 4 elements (zero padded), so
+        # that every segment starts 16-B aligned as the kernels require whatever O*I is.
+        oi = centre[0][:, :, 0].numel() if centre else 0
+        slot = (oi + 3) // 4 * 4
         segs, place, total, blk = [], {}, 0, None
         for gi, g in enumerate(self.param_groups):
             for p in g["params"]:
                 if id(p) in cidx:
                     if blk is None:
                         blk = total
-                        total += al(3 * len(centre) * centre[0][:, :, 0].numel())
-                    oi = centre[0][:, :, 0].numel()
-                    segs.append((p, blk + (len(centre) + cidx[id(p)]) * oi, oi, float(g["weight_decay"]), gi))
+                        total += al(3 * len(centre) * slot)
+                    segs.append((p, blk + (len(centre) + cidx[id(p)]) * slot, oi, float(g["weight_decay"]), gi))
                     continue
                 place[id(p)] = total
                 segs.append((p, total, p.numel(), float(g["weight_decay"]), gi))
                 total += al(p.numel())
-        segs.sort(key=lambda s: s[1])          # the kernels find a segment by binary search over offsets
+        segs.sort(key=lambda s: s[1])          # the kernels advance through the segments by offset
+        return params, centre, cidx, tmaj, segs, place, total, blk, slot
+
+    def _build(self):
+        params, centre, cidx, tmaj, segs, place, total, blk, slot = self._plan()
+        dev = params[0].device
+        if not all(p.device == dev and p.dtype == torch.float32 for p in params):
+            raise RuntimeError("arcweld RAdam needs all parameters as float32 on one device")
+        if dev.type != "cuda":
+            raise RuntimeError("arcweld RAdam runs on the GPU only (no CPU fallback)")
+        al = lambda n: (n + 63) // 64 * 64      # noqa: E731
         flat_p = torch.zeros(total, device=dev)
         flat_g = torch.zeros(total, device=dev)
 
         def view(buf, p):
             if id(p) in cidx:
                 O, I, _ = p.shape
-                return buf[blk:blk + 3 * len(centre) * O * I].view(3, len(centre), O, I)[:, cidx[id(p)]].permute(1, 2, 0)
+                slots = buf[blk:blk + 3 * len(centre) * slot].view(3, len(centre), slot)
+                return slots[:, cidx[id(p)], :O * I].view(3, O, I).permute(1, 2, 0)
             o = place[id(p)]
             if id(p) in tmaj:
                 O, I, _ = p.shape

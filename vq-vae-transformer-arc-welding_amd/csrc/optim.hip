@@ -108,8 +108,13 @@ __device__ __forceinline__ float radam_one(float gr, float& pv, float& mv, float
   return pv;
 }
 
-// float4 grid-stride over the flat buffers (segments are 256-B aligned: a float4 never straddles two; the
-// alignment padding past seg_len is zero in p, g, m and v and stays zero).
+// float4 grid-stride over the flat buffers.  The contract (include/arcweld_amd.h): every segment starts 16-B aligned
+// (a multiple of 4 elements; the host guarantees it -- arcweld.optim aligns to 256 B and pads the centre-tap slots),
+// so a float4 never straddles two segments; the padding up to the next multiple of 4 past seg_len is zero in p, g, m
+// and v and stays zero.  Elements before the first segment belong to no segment (next_seg would leave s = 0 there and
+// the end test alone would take them as segment 0): here and in sumsq_kernel every thread starts at the first
+// segment's float4 instead of 0, which adds nothing to the loop (a per-element compare cost the norm pass 0.7 us of
+// 23.8); radam_ops_kernel compares per element.
 __global__ __launch_bounds__(256) void radam_kernel(float* __restrict__ p, float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v,
                                                     const int64_t* __restrict__ seg_off,
@@ -120,14 +125,17 @@ __global__ __launch_bounds__(256) void radam_kernel(float* __restrict__ p, float
                                                     const int64_t* __restrict__ step_ptr, int zero_g) {
   __shared__ int64_t s_off[MAXSEG_LDS];
   __shared__ RAdamScalars s_S;
+  const int64_t first = seg_off[0];   // a uniform (scalar) load, in flight while the table is copied
   for (int i = threadIdx.x; i < nseg; i += blockDim.x) s_off[i] = seg_off[i];
   if (step_ptr && threadIdx.x == 0) s_S = radam_scalars(*step_ptr, S.lr, S.beta1, S.beta2, S.eps);
   __syncthreads();
   if (step_ptr) S = s_S;
   const float gs = gscale ? gscale[0] : 1.0f;
   const int64_t n4 = total >> 2;
+  const int64_t q_first = first > 0 ? (first + 3) >> 2 : 0;   // nothing before the first segment is a segment's
   int s = 0;
-  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += (int64_t)gridDim.x * blockDim.x) {
+  for (int64_t q = q_first + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n4;
+       q += (int64_t)gridDim.x * blockDim.x) {
     const int64_t e = q << 2;
     s = next_seg(s_off, nseg, s, e);
     if (e >= s_off[s] + seg_len[s] || !seg_active[s]) continue;
@@ -243,6 +251,7 @@ __global__ __launch_bounds__(256) void radam_ops_kernel(float* __restrict__ p, f
                                                         const aw_operand_desc* __restrict__ ops, int zero_g) {
   __shared__ int s_off[MAXSEG_LDS], s_end[MAXSEG_LDS];
   __shared__ RAdamScalars s_S;
+  const int first = (int)seg_off[0];   // a uniform (scalar) load, in flight while the table is copied
   load_segs32(seg_off, seg_len, seg_active, nseg, s_off, s_end);
   if (step_ptr && threadIdx.x == 0) s_S = radam_scalars(*step_ptr, S.lr, S.beta1, S.beta2, S.eps);
   __syncthreads();
@@ -254,7 +263,9 @@ __global__ __launch_bounds__(256) void radam_ops_kernel(float* __restrict__ p, f
     const int e = q << 2;
     s = next_seg(s_off, nseg, s, e);
     const int end = s_end[s];
-    if (e >= end) continue;   // past the segment's live part (or an inactive segment): no global read decides it
+    // before the first segment, past the segment's live part, or an inactive segment: no global read decides it
+    // (the extra compare is within the run-to-run spread of this kernel: 108.5 vs 108.7 us)
+    if (e < first || e >= end) continue;
     const float wd = seg_wd[s];
     const float4 g4 = reinterpret_cast<const float4*>(g)[q];
     float4 p4 = reinterpret_cast<const float4*>(p)[q];
@@ -300,14 +311,16 @@ __global__ __launch_bounds__(NT) void sumsq_kernel(const float* __restrict__ g, 
                                                     const int* __restrict__ seg_active, int nseg, int64_t total,
                                                     double* ws) {
   __shared__ int64_t s_off[MAXSEG_LDS], s_end[MAXSEG_LDS];
+  const int64_t first = seg_off[0];   // a uniform (scalar) load, in flight while the table is copied
   load_segs(seg_off, seg_len, seg_active, nseg, s_off, s_end);
   __syncthreads();
   float acc = 0.f;
   const int64_t n4 = total >> 2;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t q_first = first > 0 ? (first + 3) >> 2 : 0;   // nothing before the first segment is a segment's
   int s = 0;
   // four float4 loads in flight per thread (one dependent load per iteration left the pass latency-bound)
-  for (int64_t q0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q0 < n4; q0 += 4 * stride) {
+  for (int64_t q0 = q_first + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q0 < n4; q0 += 4 * stride) {
     float4 v[4];
     bool use[4];
 #pragma unroll
