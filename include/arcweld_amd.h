@@ -9,6 +9,16 @@
  *   - `stream` is a hipStream_t passed as void*; nothing synchronises the host;
  *   - return 0 (AW_OK) or a negative status; aw_last_error() returns a thread-local message;
  *   - no allocation inside (graph-capture safe); accumulators that must start at zero are documented.
+ *
+ * One entry point per operation: when an operation gains a parameter, its prototype changes and AW_ABI_VERSION goes
+ * up; no forwarder keeps the old list alive.  The only consumer is the in-tree Python host, whose binding
+ * (arcweld/_native.py) is read from this file: integer constants are `enum { NAME = n }` or `#define AW_NAME n`,
+ * argument structs are `typedef struct { ... } aw_x;` of int / int64_t / uint64_t / uint32_t / float / double,
+ * pointers and arrays sized by those constants, and every prototype is written out in full.  Keep to that dialect;
+ * the binding refuses what it cannot read.
+ * Pairs that stay apart on purpose, because they are different kernels or algorithms and not forwarders:
+ * aw_sample_next / aw_sample_next_ex, aw_mse_finalize / _add, the aw_embed_bwd* family, aw_bn_finalize /
+ * aw_bn_group_finalize, aw_gemm / aw_gemm_ws / aw_gemm_grouped, aw_weight_relayout / _batch.
  */
 #ifndef ARCWELD_AMD_H
 #define ARCWELD_AMD_H
@@ -26,6 +36,9 @@ enum { AW_F32 = 0, AW_BF16 = 1 };
 enum { AW_ACT_GELU_ERF = 0, AW_ACT_GELU_TANH = 1, AW_ACT_DERIV = 2 };
 
 const char* aw_last_error(void);
+/* aw_version() returns the AW_ABI_VERSION the library was built from; the host refuses a library that reports another
+ * (names outlive their parameter lists, so a stale build would be called with the wrong arguments). */
+#define AW_ABI_VERSION 2
 int aw_version(void);
 
 /* ------------------------------------------------------------------------------------------------ GEMM
@@ -176,7 +189,7 @@ int aw_wgrad_set_spin_limit(int polls);
  * ConvTranspose1d(H -> H, kernel = stride = tail_k1) that follows the decoder stack, run on x_R while it is still in
  * LDS: for tap j < tail_k1
  *   tail_y[row][j * H + c] = bf16(x_R[row] . W_j[c] + tail_bias[c])          (tail_y: [N][tail_k1 * H] bf16)
- * with tail_w[j] the forward copy of the [out][in] matrix W_j packed as a taps = 1 matrix (aw_res_pack_weights_mixed),
+ * with tail_w[j] the forward copy of the [out][in] matrix W_j packed as a taps = 1 matrix (aw_res_pack_weights, job_taps),
  * and tail_colstats (f64, 2 * H, may be NULL) += the column sums of v and v * v over the rows < N and the tail_k1
  * taps, from the f32 values before the bf16 rounding -- what aw_gemm with bias_mod = stats_mod = H computes on
  * a[R-1] and the [tail_k1 * H][H] operand copy, without the launch and without reading x_R back.  a[R-1] is still
@@ -265,50 +278,39 @@ int aw_res_dropout_masks(int64_t N, int R, float drop_p, const uint64_t* drop_se
  * the backward operand A[i][(j, o)] = W[o][j * 512 + i] (W^T for taps = 1); either may be NULL.  Packed layout of a
  * [512][K] A (row m, column k): the 1-KB block (m / 16, k / 32) at byte ((m / 16) * (K / 32) + k / 32) * 1024 holds
  * lane l = (m % 16) + 16 ((k % 32) / 8) at 16 l, element k % 8 within -- one MFMA A-fragment, so a wave reads each
- * fragment as one contiguous KB. */
-#define AW_RES_PACK_MAX 32
-int aw_res_pack_weights(const void* const* src, void* const* fwd, void* const* bwd, int n, int taps, void* stream);
-/* The same launch with a tap count per job: job_taps[i] is `taps` or 1 (NULL: all `taps`).  A 1-tap job packs a
- * [512][512] matrix beside the launch's [512][taps * 512] ones -- the chain tail's matrices ride in the decoder's
+ * fragment as one contiguous KB.
+ * job_taps (NULL: every job has `taps`) gives a tap count per job, `taps` or 1.  A 1-tap job packs a [512][512] matrix,
+ * forward copy only, beside the launch's [512][taps * 512] ones -- the chain tail's matrices ride in the decoder's
  * forward pack launch. */
-int aw_res_pack_weights_mixed(const void* const* src, void* const* fwd, void* const* bwd, const int* job_taps, int n,
-                              int taps, void* stream);
+#define AW_RES_PACK_MAX 32
+int aw_res_pack_weights(const void* const* src, void* const* fwd, void* const* bwd, const int* job_taps, int n,
+                        int taps, void* stream);
 
 /* -------------------------------------------------------------------------------- vector quantizer
  * VectorQuantizer.forward (model/vector_quantizer.py:76-119), fp32, codebook staged in LDS, no MFMA:
  *   dist = fl(fl(|z|^2 + |e_k|^2) - 2 * (k-ordered fmaf chain z.e_k)), argmin with first-index ties,
  *   z_q_ste = z + (e_idx - z), idx (int64), counts[k] += 1, sqerr[0] += sum (e_idx - z)^2 (f64).
- * counts (K floats) and sqerr (1 double) must be zero on entry.  D in {16,32,64,128,256}.
+ * sqerr (1 double) must be zero on entry.  D in {16,32,64,128,256}.
+ * counts: count_groups (1..AW_VQ_COUNT_GROUPS_MAX) partial histograms of K floats each, zero on entry; workgroup b adds
+ * into partial b % count_groups, so the adds into any one address are count_groups times fewer (they serialise at the
+ * memory-side atomic units).  The partials sum to the counts; aw_vq_finalize takes them as they are.
+ * zq_copy (NULL = none; 16-B aligned, copy_dtype AW_BF16 or AW_F32) also receives z_q_ste: the GEMM operand of the
+ * decoder's first conv, without a separate cast launch.
  */
-int aw_vq_forward(const float* z, const float* E, int64_t N, int K, int D,
-                  float* zq, int64_t* idx, float* counts, double* sqerr, void* stream);
-/* aw_vq_forward that also writes z_q_ste into zq_copy (NULL = none; 16-B aligned, copy_dtype AW_BF16 or AW_F32):
- * the GEMM operand of the decoder's first conv, without a separate cast launch. */
-int aw_vq_forward_ex(const float* z, const float* E, int64_t N, int K, int D, float* zq, int64_t* idx, float* counts,
-                     double* sqerr, void* zq_copy, int copy_dtype, void* stream);
-/* aw_vq_forward_ex with the code counts split over count_groups partial histograms (1..AW_VQ_COUNT_GROUPS_MAX):
- * counts holds count_groups x K floats, zero on entry; workgroup b adds into partial b % count_groups, so the adds
- * into any one address are count_groups times fewer (they serialise at the memory-side atomic units).  The partials
- * sum to the counts; aw_vq_finalize_ex takes them as they are. */
 #define AW_VQ_COUNT_GROUPS_MAX 64
-int aw_vq_forward_ex2(const float* z, const float* E, int64_t N, int K, int D, float* zq, int64_t* idx, float* counts,
-                      int count_groups, double* sqerr, void* zq_copy, int copy_dtype, void* stream);
+int aw_vq_forward(const float* z, const float* E, int64_t N, int K, int D, float* zq, int64_t* idx, float* counts,
+                  int count_groups, double* sqerr, void* zq_copy, int copy_dtype, void* stream);
 /* loss = m + beta*m with m = sqerr/(N*D) (vector_quantizer.py:107-108); perplexity = exp(-sum p log(p+1e-10)),
- * p = counts/N (:114-115).  Each output is one f32 device scalar. */
-int aw_vq_finalize(const float* counts, const double* sqerr, int64_t N, int K, int D, float beta,
+ * p = counts/N (:114-115), counts = the count_groups partial histograms of aw_vq_forward summed per code in a fixed
+ * order.  Each output is one f32 device scalar. */
+int aw_vq_finalize(const float* counts, int count_groups, const double* sqerr, int64_t N, int K, int D, float beta,
                    float* loss, float* perplexity, void* stream);
-/* aw_vq_finalize over count_groups partial histograms (aw_vq_forward_ex2), summed per code in a fixed order. */
-int aw_vq_finalize_ex(const float* counts, int count_groups, const double* sqerr, int64_t N, int K, int D, float beta,
-                      float* loss, float* perplexity, void* stream);
 /* Backward of the STE + loss: dz = g_zq + g_loss*2(z - z_q)/(N*D);  dE[idx] += g_loss*2*beta*(z_q - z)/(N*D).
- * g_zq may be NULL (treated as 0); g_loss is a device scalar.  dE is accumulated (not overwritten). */
+ * g_zq may be NULL (treated as 0); g_loss is a device scalar.  dE is accumulated (not overwritten).
+ * dz_copy (NULL = none; copy_dtype AW_BF16 or AW_F32) also receives dz: the operand of the SepCNN backward GEMMs. */
 int aw_vq_backward(const float* z, const float* E, const int64_t* idx, const float* g_zq, const float* g_loss,
-                   int64_t N, int K, int D, float beta, float* dz, float* dE, void* stream);
-/* aw_vq_backward that also writes dz into dz_copy (NULL = none; copy_dtype AW_BF16 or AW_F32): the operand of the
- * SepCNN backward GEMMs. */
-int aw_vq_backward_ex(const float* z, const float* E, const int64_t* idx, const float* g_zq, const float* g_loss,
-                      int64_t N, int K, int D, float beta, float* dz, float* dE, void* dz_copy, int copy_dtype,
-                      void* stream);
+                   int64_t N, int K, int D, float beta, float* dz, float* dE, void* dz_copy, int copy_dtype,
+                   void* stream);
 /* ------------------------------------------------------------------ residual VQ with EMA codebooks (csrc/rvq.hip)
  * ResidualVQLightning (model/vector_quantizer.py:9-56) wraps vector-quantize-pytorch's ResidualVQ (third-party, not
  * installed here: its published algorithm is restated, parity unpinned).  Per layer i: aw_vq_forward on residual r_i
@@ -376,9 +378,12 @@ int aw_weight_grad_scatter(const float* g, int O, int I, int k, int tap, int mod
 int aw_cast(const float* in, int64_t n, void* out, int dtype, void* stream);
 
 /* Un-patch head forward (vq_vae_patch_embedd.py:27-30,52-57):
- * y (R = B*Q rows of H, f32, BN input) -> BN(stats) -> GELU(erf) -> ConvT(H->1, k5, s5) -> x_hat (B, 200, 2)
- * interleaved (flat position 5q+j of window b).  stats (f32 4*H): mean, invstd, gamma, beta (aw_bn_finalize). */
-int aw_unpatch_head_fwd(const float* y, int64_t R, int H, int Q, const float* stats, const float* w2,
+ * y (R = B*Q rows of H, y_dtype, BN input) -> BN(stats) -> GELU(erf) -> ConvT(H->1, k5, s5) -> x_hat (B, 200, 2)
+ * interleaved (flat position 5q+j of window b).  stats (f32 4*H): mean, invstd, gamma, beta (aw_bn_finalize).
+ * y_dtype, here and in the two backward passes: AW_F32, or AW_BF16 when H is a power of two in 64..2048 -- the bf16
+ * operand mode stores the ConvT output in bf16, halving the head's three HBM passes over it; the BN statistics still
+ * come from the f32 values in the ConvT epilogue. */
+int aw_unpatch_head_fwd(const void* y, int y_dtype, int64_t R, int H, int Q, const float* stats, const float* w2,
                         const float* b2, float* x_hat, void* stream);
 /* BatchNorm finalize: colstats (f64 sum, sumsq over n rows) -> stats {mean, invstd, gamma, beta};
  * training: running_mean/var momentum update (unbiased var), *nbt += 1.  eval (training == 0): uses running. */
@@ -390,28 +395,17 @@ int aw_bn_finalize(const double* colstats, int64_t n, int H, const float* gamma,
  *         accumulated (+=).
  * pass 2: g_y (R x H, gy_dtype) = BatchNorm backward (batch stats if training, else running) of g*gelu'(.),
  *         db_y (H f32, +=) = channel sums of g_y (gradient of the ConvT bias feeding the BN). */
-int aw_unpatch_head_bwd1(const float* y, int64_t R, int H, int Q, const float* stats, const float* w2,
+int aw_unpatch_head_bwd1(const void* y, int y_dtype, int64_t R, int H, int Q, const float* stats, const float* w2,
                          const float* g_xhat, double* gsums, float* gw2, float* gb2, float* ggamma, float* gbeta,
                          void* stream);
-int aw_unpatch_head_bwd2(const float* y, int64_t R, int H, int Q, const float* stats, const float* w2,
+int aw_unpatch_head_bwd2(const void* y, int y_dtype, int64_t R, int H, int Q, const float* stats, const float* w2,
                          const float* g_xhat, const double* gsums, int training, void* g_y, int gy_dtype, float* db_y,
                          void* stream);
-/* The same three passes with y in y_dtype (AW_F32, or AW_BF16 when H is a power of two in 64..2048): the bf16
- * operand mode stores the ConvT output in bf16, halving the head's three HBM passes over it; the BN statistics
- * still come from the f32 values in the ConvT epilogue. */
-int aw_unpatch_head_fwd_ex(const void* y, int y_dtype, int64_t R, int H, int Q, const float* stats, const float* w2,
-                           const float* b2, float* x_hat, void* stream);
-int aw_unpatch_head_bwd1_ex(const void* y, int y_dtype, int64_t R, int H, int Q, const float* stats, const float* w2,
-                            const float* g_xhat, double* gsums, float* gw2, float* gb2, float* ggamma, float* gbeta,
-                            void* stream);
-int aw_unpatch_head_bwd2_ex(const void* y, int y_dtype, int64_t R, int H, int Q, const float* stats, const float* w2,
-                            const float* g_xhat, const double* gsums, int training, void* g_y, int gy_dtype,
-                            float* db_y, void* stream);
 /* Fused training-step form of the head forward and pass 1 (train_reconstruction_embedding.py's step: loss =
  * mse(x_hat, x) + embedding loss, autencoder_lightning_base.py:80-97; vq_vae_patch_embedd.py:27-30,52-57), H == 512:
- * one read of y computes x_hat (as aw_unpatch_head_fwd_ex), g_xhat = (2 / (R*5)) * gscale[0] * (x_hat - x) (as
+ * one read of y computes x_hat (as aw_unpatch_head_fwd), g_xhat = (2 / (R*5)) * gscale[0] * (x_hat - x) (as
  * aw_mse_bwd), sqerr (f64, +=) = sum (x_hat - x)^2 (as aw_mse_fwd), and pass 1 of the backward from that g_xhat
- * (as aw_unpatch_head_bwd1_ex: gsums, gw2, gb2, ggamma, gbeta).  x: the input windows, same layout as x_hat. */
+ * (as aw_unpatch_head_bwd1: gsums, gw2, gb2, ggamma, gbeta).  x: the input windows, same layout as x_hat. */
 int aw_unpatch_head_fwd_bwd1(const void* y, int y_dtype, int64_t R, int H, int Q, const float* stats, const float* w2,
                              const float* b2, const float* x, const float* gscale, float* x_hat, float* g_xhat,
                              double* sqerr, double* gsums, float* gw2, float* gb2, float* ggamma, float* gbeta,
@@ -463,37 +457,30 @@ int aw_mse_finalize_add(const double* sqerr, int64_t numel, const float* addend,
  * Nothing outside those float4s is read or written: the elements before the first segment, the gaps between
  * segments and inactive segments may hold anything.
  * scalars come from host (step count, lr, betas, eps); `gscale` is a device scalar multiplying the gradient
- * first (clip coefficient; NULL = 1). */
-int aw_radam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, const int64_t* seg_off,
-                  const int64_t* seg_len, const float* seg_wd, const int* seg_active, int nseg, int64_t total, int64_t step,
-                  float lr, float beta1, float beta2, float eps, const float* gscale, const int64_t* step_ptr,
-                  int zero_grad, void* stream);
-/* zero_grad != 0: the gradient of every updated element is zeroed after use (optimizer.zero_grad() fused into the
- * update; inactive segments are left as they are). */
-/* aw_radam_step that also writes the operand copies of the updated weights (what aw_weight_relayout_batch would
- * produce from the new values), so the training step needs no relayout launch.  ops: device array of
- * AW_OPS_PER_SEG descriptors per segment (ops[AW_OPS_PER_SEG*s + j]; mode -1 = none): flat element l of segment s
- * (the parameter in its storage order: (O, I, k) contiguous; a declare_centre_tap segment is its [O][I] centre,
- * described as k = 1, tap = 0) goes to `out` at the index of relayout mode `mode` (0-7), cast to `dtype`. */
+ * first (clip coefficient; NULL = 1).  With step_ptr != NULL the step number is read from the device (the host `step`
+ * is ignored) and the bias corrections and rectification are derived there, in double precision like torch's
+ * python-float scalars.
+ * zero_grad != 0: the gradient of every updated element is zeroed after use (optimizer.zero_grad() fused into the
+ * update; inactive segments are left as they are).
+ * ops != NULL (total < 2^31): the update also writes the operand copies of the updated weights (what
+ * aw_weight_relayout_batch would produce from the new values), so the training step needs no relayout launch.  ops:
+ * device array of AW_OPS_PER_SEG descriptors per segment (ops[AW_OPS_PER_SEG*s + j]; mode -1 = none): flat element l
+ * of segment s (the parameter in its storage order: (O, I, k) contiguous; a declare_centre_tap segment is its [O][I]
+ * centre, described as k = 1, tap = 0) goes to `out` at the index of relayout mode `mode` (0-7), cast to `dtype`. */
 #define AW_OPS_PER_SEG 2
 typedef struct {
   void* out;
   int O, I, k, tap, mode, dtype;
   int64_t ldo;
 } aw_operand_desc;
-int aw_radam_step_ops(float* param, float* grad, float* exp_avg, float* exp_avg_sq, const int64_t* seg_off,
-                      const int64_t* seg_len, const float* seg_wd, const int* seg_active, int nseg, int64_t total,
-                      int64_t step, float lr, float beta1, float beta2, float eps, const float* gscale,
-                      const int64_t* step_ptr, const aw_operand_desc* ops, int zero_grad, void* stream);
-/* Device step counter / RNG counter: *counter += v (one thread; graph-capture safe).  With step_ptr != NULL,
- * aw_radam_step reads the step number from the device (the host `step` is ignored) and derives the bias
- * corrections and rectification there, in double precision like torch's python-float scalars. */
-int aw_counter_add(int64_t* counter, int64_t v, void* stream);
-/* The same, also copying the new value to *snapshot (the per-forward dropout seed the backward re-reads). */
-int aw_counter_add_snapshot(int64_t* counter, int64_t v, int64_t* snapshot, void* stream);
-/* The same, also zeroing zero[0 .. nzero) in the one launch (a forward's f64 accumulator block). */
-int aw_counter_add_snapshot_zero(int64_t* counter, int64_t v, int64_t* snapshot, double* zero, int64_t nzero,
-                                 void* stream);
+int aw_radam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, const int64_t* seg_off,
+                  const int64_t* seg_len, const float* seg_wd, const int* seg_active, int nseg, int64_t total, int64_t step,
+                  float lr, float beta1, float beta2, float eps, const float* gscale, const int64_t* step_ptr,
+                  const aw_operand_desc* ops, int zero_grad, void* stream);
+/* Device step counter / RNG counter: *counter += v (graph-capture safe).  snapshot (may be NULL) also receives the new
+ * value (the per-forward dropout seed the backward re-reads).  zero (may be NULL; needs snapshot) names a block
+ * zero[0 .. nzero) of f64 accumulators that the same launch zeroes (a forward's accumulator block). */
+int aw_counter_add(int64_t* counter, int64_t v, int64_t* snapshot, double* zero, int64_t nzero, void* stream);
 /* Global L2 norm of the active segments of `grad` -> out_norm (f32 device scalar) and the clip coefficient
  * min(max_norm/(norm+1e-6), 1) -> out_coef (Lightning gradient_clip_val -> clip_grad_norm_).
  * ws: f64[AW_NORM_WS] scratch (per-workgroup partial sums, reduced in a fixed order: the norm is deterministic). */
@@ -542,21 +529,17 @@ int aw_embed_sort(const int64_t* ids, int64_t R, int V, int* work, void* stream)
 int aw_embed_bwd_segsum(const int* work, int V, int D, const float* dx, float* dwtok, void* stream);
 /* Causal self-attention core (model/transformer_block.py:44-60) on the packed qkv projection
  * (B*T, 3*d, dtype), heads of hs = d/n_head: y (B*T, d, dtype) = softmax(q k^T / sqrt(hs), causal) v;
- * lse (B*n_head*T f32) saved for the backward (flash-style, T x T never materialised). */
-int aw_attn_fwd(const void* qkv, int64_t B, int T, int n_head, int d, int dtype, void* y, float* lse,
-                void* stream);
+ * lse (B*n_head*T f32) saved for the backward (flash-style, T x T never materialised).
+ * Attention-probability dropout (CausalSelfAttention.attn_dropout, transformer_block.py:44-57; the reference default
+ * is 0.0): P_ij kept with probability 1 - drop_p and scaled by 1/(1 - drop_p); the mask of element
+ * ((b*n_head + h)*T + i)*T + j comes from the counter hash of (drop_seed mixed with *seed_ptr when given), so the
+ * backward regenerates the forward's mask.  drop_p = 0: no dropout, drop_seed and seed_ptr are not used. */
+int aw_attn_fwd(const void* qkv, int64_t B, int T, int n_head, int d, int dtype, void* y, float* lse, float drop_p,
+                uint64_t drop_seed, const uint64_t* seed_ptr, void* stream);
 /* dqkv (B*T, 3d, dtype) from dy (B*T, d, dtype), recomputing P from lse; ws: f32 B*n_head*T (delta). */
 int aw_attn_bwd(const void* qkv, const void* y, const void* dy, const float* lse, int64_t B, int T, int n_head,
-                int d, int dtype, void* dqkv, float* ws, void* stream);
-/* The same two with attention-probability dropout (CausalSelfAttention.attn_dropout, transformer_block.py:44-57;
- * the reference default is 0.0): P_ij kept with probability 1 - drop_p and scaled by 1/(1 - drop_p); the mask of
- * element ((b*n_head + h)*T + i)*T + j comes from the counter hash of (drop_seed mixed with *seed_ptr when given),
- * so the backward regenerates the forward's mask.  drop_p = 0 is exactly aw_attn_fwd / aw_attn_bwd. */
-int aw_attn_fwd_dropout(const void* qkv, int64_t B, int T, int n_head, int d, int dtype, void* y, float* lse,
-                        float drop_p, uint64_t drop_seed, const uint64_t* seed_ptr, void* stream);
-int aw_attn_bwd_dropout(const void* qkv, const void* y, const void* dy, const float* lse, int64_t B, int T,
-                        int n_head, int d, int dtype, void* dqkv, float* ws, float drop_p, uint64_t drop_seed,
-                        const uint64_t* seed_ptr, void* stream);
+                int d, int dtype, void* dqkv, float* ws, float drop_p, uint64_t drop_seed, const uint64_t* seed_ptr,
+                void* stream);
 /* KV-cache decode attention (MyTransformerDecoder.generate, model/transformer_decoder.py:203-224):
  * n_new query rows per sequence at absolute positions pos0 .. pos0+n_new-1 (qkv_new (B*n_new, 3d, dtype), row
  * b*n_new + i).  Their K and V are appended to kv_cache (B, Tmax, 2d, dtype; row b*Tmax + t = [K | V]) and

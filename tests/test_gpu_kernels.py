@@ -269,7 +269,7 @@ def test_vq_small_forward_backward_vs_reference(K):
 @pytest.mark.parametrize("cdt", [torch.bfloat16, torch.float32])
 @pytest.mark.parametrize("Kc,D,N", [(512, 64, 16384), (64, 16, 1000)])
 def test_vq_operand_copies_match_the_cast_outputs(K, cdt, Kc, D, N):
-    """aw_vq_forward_ex / aw_vq_backward_ex: the operand copies are exactly the cast of z_q and dz (the step's cast
+    """aw_vq_forward / aw_vq_backward with zq_copy / dz_copy: the operand copies are exactly the cast of z_q and dz (the step's cast
     launches they replace), and the primary outputs are unchanged by writing them."""
     z = torch.tensor(gen.normal(301, (N, D), 0.08), device=DEV)
     E = torch.tensor(gen.normal(302, (Kc, D), 0.08), device=DEV)
@@ -297,7 +297,7 @@ def test_vq_operand_copies_match_the_cast_outputs(K, cdt, Kc, D, N):
 @pytest.mark.parametrize("Kc,D,N", [(512, 64, 16384), (512, 64, 1000), (64, 16, 1000), (8192, 256, 4096)])
 @pytest.mark.parametrize("G", [2, 8])
 def test_vq_grouped_counts_sum_to_the_counts(K, Kc, D, N, G):
-    """aw_vq_forward_ex2 / aw_vq_finalize_ex: the count_groups partial histograms sum exactly to the count_groups 1
+    """aw_vq_forward / aw_vq_finalize: the count_groups partial histograms sum exactly to the count_groups 1
     counts (both kernels: pinned MFMA at K <= 512, streaming VALU above), every other output is unchanged, and the
     finalize over the partials gives the same loss and perplexity bits."""
     z = torch.tensor(gen.normal(311, (N, D), 0.08), device=DEV)
@@ -450,7 +450,7 @@ def test_mse_loss_vs_fp64(K, n, off):
 
 def test_mse_finalize_add_and_counter_zero(K):
     """aw_mse_finalize_add (recon = sq / n, loss = recon + embedding loss in one launch) and
-    aw_counter_add_snapshot_zero (dropout counter advance + snapshot + accumulator-block zeroing in one launch)."""
+    aw_counter_add with snapshot and zero (dropout counter advance + snapshot + accumulator-block zeroing in one launch)."""
     sq = torch.tensor([1234.5], device=DEV, dtype=torch.float64)
     emb = torch.tensor([0.25], device=DEV)
     recon, loss = torch.empty((), device=DEV), torch.empty((), device=DEV)
@@ -630,7 +630,7 @@ def test_wgrad_batch_broken_handoff_poisons_the_tile():
 
 @pytest.mark.parametrize("training", [True, False])
 def test_unpatch_head_bf16_y_equals_f32_y(training):
-    """aw_unpatch_head_*_ex with the ConvT output in bf16 (the bf16 operand mode, model/vq_vae_patch_embedd.py:24-31)
+    """aw_unpatch_head_* with the ConvT output in bf16 (the bf16 operand mode, model/vq_vae_patch_embedd.py:24-31)
     computes exactly what the f32 passes compute on the same (bf16-representable) values: x_hat, the ConvT2 / BN
     gradients, the per-channel sums and g_y are bit-identical."""
     from arcweld import kernels as K

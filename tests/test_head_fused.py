@@ -1,6 +1,6 @@
 """The fused training-step head (aw_unpatch_head_fwd_bwd1: forward + MSE value / gradient + backward pass 1 in one read
-of the ConvT output) against the separate passes it replaces (aw_unpatch_head_fwd_ex, aw_mse_fwd, aw_mse_bwd,
-aw_unpatch_head_bwd1_ex) on the same inputs; model/vq_vae_patch_embedd.py:27-30,52-57 and
+of the ConvT output) against the separate passes it replaces (aw_unpatch_head_fwd, aw_mse_fwd, aw_mse_bwd,
+aw_unpatch_head_bwd1) on the same inputs; model/vq_vae_patch_embedd.py:27-30,52-57 and
 autencoder_lightning_base.py:80-97 define the math both follow."""
 import pytest
 import torch

@@ -1,4 +1,4 @@
-"""Persistent weight operands kept current by the optimizer (arcweld/operands.py, aw_radam_step_ops): the update
+"""Persistent weight operands kept current by the optimizer (arcweld/operands.py, aw_radam_step with ops): the update
 kernel's cast copies equal a fresh aw_weight_relayout_batch of the updated weights (every relayout mode the step
 uses, bf16 and fp32 operands, H = 64 and the configs[1] width H = 512), training with them follows the per-forward
 relayout trajectory (to the run-to-run noise of the weight-gradient atomics), and a maintained step issues no relayout launch."""

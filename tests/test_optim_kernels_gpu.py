@@ -1,4 +1,4 @@
-"""csrc/optim.hip (aw_radam_step, aw_radam_step_ops, aw_grad_norm_clip, aw_scale) and the weight-relayout family of
+"""csrc/optim.hip (aw_radam_step with and without ops, aw_grad_norm_clip, aw_scale) and the weight-relayout family of
 csrc/vqvae.hip (aw_weight_relayout, aw_weight_relayout_batch, aw_weight_grad_scatter, aw_cast) against the fp64
 restatements and the permute-built index maps of tests/optim_refs.py.  The kernels are called directly through
 arcweld.kernels.  Every buffer a kernel may write sits between canary margins that are checked after every launch; the
@@ -114,7 +114,7 @@ def _state(name, kind):
 
 
 def _launch(L, st, step, betas, src, gs, zero_grad=False, ops=None, host_step=None, T=None):
-    """One aw_radam_step / aw_radam_step_ops launch from the state `st`; the four buffers afterwards (numpy)."""
+    """One aw_radam_step launch (with ops when given) from the state `st`; the four buffers afterwards (numpy)."""
     from arcweld import kernels as K
     T = T or _Table(L)
     b = types.SimpleNamespace(p=_Buf(st.p), g=_Buf(st.g), m=_Buf(st.m), v=_Buf(st.v))

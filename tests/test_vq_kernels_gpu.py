@@ -1,4 +1,4 @@
-"""csrc/vq.hip -- the nearest-code search behind aw_vq_forward_ex2 (both kernels), vq_finalize, vq_backward and
+"""csrc/vq.hip -- the nearest-code search behind aw_vq_forward (both kernels), vq_finalize, vq_backward and
 vq_onehot -- against the fp64 restatements of tests/vq_refs.py, at ragged K and N, every reachable instantiation and
 both count paths.  Every buffer sits between margins: z and E inside NaN-filled allocations (a read outside them
 surfaces as a NaN distance, which is never taken -- a wrong code), every output between canaries that are checked
@@ -10,7 +10,7 @@ Random block: the derived bound of vq_refs.eps on every row; the two kernels are
 norm chains round differently).  The allowances are derived in vq_refs.py and measured on the CPU in
 tests/test_vq_refs_cpu.py.
 
-Which exact case reaches which kernel (aw_vq_forward_ex2's dispatch: pinned when K <= 512 and D in 16 / 32 / 64, else
+Which exact case reaches which kernel (aw_vq_forward's dispatch: pinned when K <= 512 and D in 16 / 32 / 64, else
 streaming with 32-row workgroups (RPL 4) when N < 32768 and D <= 64, 64-row ones (RPL 8) otherwise):
   pinned<16>       (1, 16, 1) (65, 16, 65) (509, 16, 63)         pinned<32>   (3, 32, 63) (100, 32, 200) (512, 32, 64)
   pinned<64>       (64, 64, 64) (509, 64, 65) (512, 64, 200) (100, 64, 1)
@@ -76,7 +76,7 @@ def _place(a):
 
 
 def _forward(z, E, groups=1, copy=None, zd=None, Ed=None):
-    """One aw_vq_forward_ex2 launch; the outputs (as _Out) after the canary checks."""
+    """One aw_vq_forward launch; the outputs (as _Out) after the canary checks."""
     from arcweld import kernels as K
     (N, D), Kc = z.shape, len(E)
     o = types.SimpleNamespace(zq=_Out((N, D)), idx=_Out((N,), torch.int64), counts=_Out((groups * Kc,), fill=0.0),
@@ -90,7 +90,7 @@ def _forward(z, E, groups=1, copy=None, zd=None, Ed=None):
 
 
 def _finalize(counts, sqerr, N, Kc, D, groups):
-    """(loss, perplexity) of aw_vq_finalize_ex over host counts (groups * K,) and an f64 sqerr."""
+    """(loss, perplexity) of aw_vq_finalize over host counts (groups * K,) and an f64 sqerr."""
     from arcweld import kernels as K
     c = _Out((groups * Kc,))
     c.t.copy_(torch.as_tensor(np.asarray(counts, np.float32)))

@@ -1,6 +1,8 @@
 #!/bin/bash
 # Same-box A/B of two library builds: alternating bench runs (VQ-VAE line + transformer line), ARCWELD_LIB selects
 # the build.  usage: [OUT=dir] bash tools/ab_bench.sh <libA.so> <libB.so> [rounds]
+# Both builds must have this tree's AW_ABI_VERSION (the host refuses any other library): an A/B across an ABI change
+# needs two trees, each running its own bench.py against its own build.
 set -o pipefail
 A=$1; B=$2; R=${3:-2}
 OUT=${OUT:-build/ab}

@@ -21,15 +21,16 @@ counts = torch.zeros(Kc, device="cuda")
 sq = torch.zeros(1, device="cuda", dtype=torch.float64)
 s = torch.cuda.current_stream().cuda_stream
 P = ctypes.c_void_p
+# aw_vq_forward(z, E, N, K, D, zq, idx, counts, count_groups, sqerr, zq_copy, copy_dtype, stream): one histogram, no copy
+ARGS = (P(z.data_ptr()), P(E.data_ptr()), ctypes.c_int64(N), Kc, D, P(zq.data_ptr()), P(idx.data_ptr()),
+        P(counts.data_ptr()), 1, P(sq.data_ptr()), P(None), 0, P(s))
 for _ in range(5):
-    assert lib.aw_vq_forward(P(z.data_ptr()), P(E.data_ptr()), ctypes.c_int64(N), Kc, D, P(zq.data_ptr()),
-                             P(idx.data_ptr()), P(counts.data_ptr()), P(sq.data_ptr()), P(s)) == 0
+    assert lib.aw_vq_forward(*ARGS) == 0
 torch.cuda.synchronize()
 ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
 ev[0].record()
 for _ in range(20):
-    lib.aw_vq_forward(P(z.data_ptr()), P(E.data_ptr()), ctypes.c_int64(N), Kc, D, P(zq.data_ptr()),
-                      P(idx.data_ptr()), P(counts.data_ptr()), P(sq.data_ptr()), P(s))
+    lib.aw_vq_forward(*ARGS)
 ev[1].record()
 torch.cuda.synchronize()
 print(f"{NAME}: {ev[0].elapsed_time(ev[1]) / 20 * 1e3:.1f} us per launch (events, 20 back to back)")

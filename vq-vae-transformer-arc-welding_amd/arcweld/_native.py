@@ -1,4 +1,7 @@
-"""ctypes binding of the HIP C ABI (include/arcweld_amd.h).
+"""ctypes binding of the HIP C ABI, read from include/arcweld_amd.h at import.
+
+The header is the single source of the binding: its integer constants, argument structs and prototypes are parsed
+here (``parse_header``), nothing is mirrored by hand.  What the parser cannot read it refuses (NativeError).
 
 The library is loaded AFTER ``import torch`` so that its ``libamdhip64.so.7`` dependency resolves (by SONAME) to
 the HIP runtime torch already loaded: device pointers, streams and the caching allocator are then shared.
@@ -8,253 +11,152 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 
 import torch  # noqa: F401  (must precede the library load, see module docstring)
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# ARCWELD_LIB overrides the library path (A/B timing of two builds in one process tree: tools/ab_bench.sh)
+# ARCWELD_LIB overrides the library path (A/B timing of two builds of one ABI in one process tree: tools/ab_bench.sh)
 LIB_PATH = os.environ.get("ARCWELD_LIB") or os.path.join(PKG_DIR, "lib", "libarcweld_amd.so")
 HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "arcweld_amd.h")
-
-AW_F32, AW_BF16 = 0, 1
-AW_ACT_GELU_ERF, AW_ACT_GELU_TANH, AW_ACT_DERIV = 0, 1, 2
-AW_STORE_NT, AW_STORE_WT = 0, 1   # aw_gemm_args.store_policy
-
-c_i64 = ctypes.c_int64
-c_int = ctypes.c_int
-c_f = ctypes.c_float
-c_p = ctypes.c_void_p
-
-
-class GemmArgs(ctypes.Structure):
-    _fields_ = [
-        ("M", c_int), ("N", c_int), ("K", c_int),
-        ("a_dtype", c_int),
-        ("A", c_p), ("lda", c_i64), ("a_trans", c_int),
-        ("B", c_p), ("ldb", c_i64), ("b_trans", c_int),
-        ("conv_cin", c_int), ("conv_seg", c_int), ("conv_dir", c_int), ("conv_operand", c_int),
-        ("alpha", c_f), ("beta", c_f),
-        ("bias", c_p),
-        ("act", c_int),
-        ("pre", c_p), ("ld_pre", c_i64),
-        ("resid", c_p), ("ld_resid", c_i64),
-        ("drop_p", c_f), ("drop_seed", ctypes.c_uint64),
-        ("C", c_p), ("ldc", c_i64), ("c_dtype", c_int),
-        ("C2", c_p), ("ldc2", c_i64), ("c2_mode", c_int), ("c2_dtype", c_int),
-        ("drop2_p", c_f), ("drop2_seed", ctypes.c_uint64),
-        ("colstats", c_p), ("stats_mod", c_int),
-        ("a_rowsum", c_p),
-        ("bias_mod", c_int),
-        ("accumulate", c_int), ("col_mod", c_int), ("col_mul", c_int), ("col_off", c_int),
-        ("seed_ptr", c_p),
-        ("pre_dtype", c_int),
-        ("store_policy", c_int),
-        ("resid_dtype", c_int),
-    ]
-
-
-class RelayoutJob(ctypes.Structure):
-    """aw_relayout_job (include/arcweld_amd.h)."""
-    _fields_ = [("W", c_p), ("out", c_p), ("O", c_int), ("I", c_int), ("k", c_int), ("tap", c_int),
-                ("mode", c_int), ("ldo", c_i64)]
-
-
-class OperandDesc(ctypes.Structure):
-    """aw_operand_desc (include/arcweld_amd.h)."""
-    _fields_ = [("out", c_p), ("O", c_int), ("I", c_int), ("k", c_int), ("tap", c_int), ("mode", c_int),
-                ("dtype", c_int), ("ldo", c_i64)]
-
-
-OPS_PER_SEG = 2     # AW_OPS_PER_SEG
-
-RES_CHAIN_MAX = 16  # AW_RES_CHAIN_MAX
-RES_PACK_MAX = 32   # AW_RES_PACK_MAX
-RES_TAIL_MAX = 8    # AW_RES_TAIL_MAX
-SAMPLE_MAX_V = 16384  # AW_SAMPLE_MAX_V
-_E = RES_CHAIN_MAX
-
-
-class ResChainFwdArgs(ctypes.Structure):
-    """aw_res_chain_fwd_args (include/arcweld_amd.h)."""
-    _fields_ = [("N", c_i64), ("H", c_int), ("R", c_int), ("taps", c_int), ("seg", c_int), ("a0", c_p), ("x0", c_p),
-                ("w1", c_p * _E), ("w2", c_p * _E), ("b1", c_p * _E), ("b2", c_p * _E),
-                ("dgelu_h", c_p * _E), ("a1", c_p * _E), ("dgelu_x", c_p * _E), ("a", c_p * _E),
-                ("drop_p", c_f), ("drop_seed", ctypes.c_uint64 * _E), ("seed_ptr", c_p), ("store_policy", c_int),
-                ("drop_masks", c_p),
-                ("tail_k1", c_int), ("tail_w", c_p * RES_TAIL_MAX), ("tail_bias", c_p), ("tail_y", c_p),
-                ("tail_colstats", c_p),
-                ("sep_d", c_int), ("sep_w", c_p), ("sep_bias", c_p), ("sep_z", c_p),
-                ("head_k", c_int), ("head_in", c_p), ("head_w", c_p), ("head_bias", c_p), ("head_patches", c_p),
-                ("head_L", c_int), ("head_C", c_int), ("head_P", c_int)]
-
-
-class ResChainBwdArgs(ctypes.Structure):
-    """aw_res_chain_bwd_args (include/arcweld_amd.h)."""
-    _fields_ = [("N", c_i64), ("H", c_int), ("R", c_int), ("taps", c_int), ("seg", c_int), ("gx", c_p), ("gxo", c_p),
-                ("x0", c_p), ("w1t", c_p * _E), ("w2t", c_p * _E), ("dgelu_h", c_p * _E), ("dgelu_x", c_p * _E),
-                ("gh", c_p * _E), ("gxo_out", c_p * _E),
-                ("drop_p", c_f), ("store_policy", c_int), ("drop_masks", c_p)]
-
-
-class SampleArgs(ctypes.Structure):
-    """aw_sample_args (include/arcweld_amd.h)."""
-    _fields_ = [("logits", c_p), ("B", c_int), ("V", c_int), ("n_valid", c_int),
-                ("top_k", c_int), ("top_p", c_f), ("min_p", c_f), ("inv_temperature", c_f),
-                ("do_sample", c_int), ("seed", ctypes.c_uint64), ("step", c_i64),
-                ("ids_out", c_p), ("ld_ids", c_i64), ("col", c_i64),
-                ("u_out", c_p),
-                ("logp_out", c_p), ("logq_out", c_p), ("ld_lp", c_i64), ("col_lp", c_i64),
-                ("n_kept_out", c_p), ("thr_out", c_p),
-                ("bad_count", c_p)]
-
-
-BEAM_MAX_W = 32       # AW_BEAM_MAX_W
-
-
-class BeamArgs(ctypes.Structure):
-    """aw_beam_args (include/arcweld_amd.h)."""
-    _fields_ = [("logits", c_p), ("ldl", c_i64), ("B", c_int), ("W_in", c_int), ("W_out", c_int), ("V", c_int),
-                ("n_valid", c_int),
-                ("scores_in", c_p),
-                ("scores_out", c_p), ("parent_out", c_p), ("token_out", c_p), ("logp_out", c_p),
-                ("bad_count", c_p)]
-
-
-ENSEMBLE_MAX_N = 64   # AW_ENSEMBLE_MAX_N
-ENSEMBLE_MAX_Q = 8    # AW_ENSEMBLE_MAX_Q
-KNN_MAX_K = 32        # AW_KNN_MAX_K
-KNN_MAX_SPLITS = 1024  # AW_KNN_MAX_SPLITS
-
-
-class EnsembleArgs(ctypes.Structure):
-    """aw_ensemble_args (include/arcweld_amd.h)."""
-    _fields_ = [("x", c_p), ("G", c_int), ("N", c_int), ("M", c_i64),
-                ("q", ctypes.POINTER(c_f)), ("Q", c_int),
-                ("mean", c_p), ("std", c_p),
-                ("quant", c_p),
-                ("y", c_p),
-                ("seg", c_i64),
-                ("crps", c_p),
-                ("cover", c_p),
-                ("bad_count", c_p)]
-
-
-# name -> argtypes (every entry returns int status except aw_last_error)
-SIGNATURES = {
-    "aw_version": [],
-    "aw_gemm": [ctypes.POINTER(GemmArgs), c_p],
-    "aw_gemm_ws": [ctypes.POINTER(GemmArgs), c_p, c_i64, c_p],
-    "aw_gemm_workspace": [ctypes.POINTER(GemmArgs)],
-    "aw_gemm_grouped": [ctypes.POINTER(GemmArgs), c_int, c_p],
-    "aw_gemm_set_tile": [c_int],
-    "aw_gemm_describe": [ctypes.POINTER(GemmArgs), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_uint32),
-                         ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)],
-    "aw_gemm_set_wgrad_policy": [c_int],
-    "aw_wgrad_batch_workspace": [ctypes.POINTER(GemmArgs), c_int],
-    "aw_wgrad_batch": [ctypes.POINTER(GemmArgs), c_int, c_p, c_i64, c_p],
-    "aw_wgrad_set_spin_limit": [c_int],
-    "aw_res_chain_fwd": [ctypes.POINTER(ResChainFwdArgs), c_p],
-    "aw_res_chain_bwd": [ctypes.POINTER(ResChainBwdArgs), c_p],
-    "aw_res_pack_weights": [ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(c_p), c_int, c_int, c_p],
-    "aw_res_pack_weights_mixed": [ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(c_p),
-                                  ctypes.POINTER(c_int), c_int, c_int, c_p],
-    "aw_res_dropout_masks_bytes": [c_i64, c_int],
-    "aw_res_dropout_masks": [c_i64, c_int, c_f, ctypes.POINTER(ctypes.c_uint64), c_p, c_p, c_p],
-    "aw_weight_relayout_batch": [ctypes.POINTER(RelayoutJob), c_int, c_int, c_p],
-    "aw_vq_forward": [c_p, c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_p],
-    "aw_vq_forward_ex": [c_p, c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_int, c_p],
-    "aw_vq_finalize": [c_p, c_p, c_i64, c_int, c_int, c_f, c_p, c_p, c_p],
-    "aw_vq_forward_ex2": [c_p, c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_int, c_p, c_p, c_int, c_p],
-    "aw_vq_finalize_ex": [c_p, c_int, c_p, c_i64, c_int, c_int, c_f, c_p, c_p, c_p],
-    "aw_vq_backward": [c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_f, c_p, c_p, c_p],
-    "aw_vq_backward_ex": [c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_f, c_p, c_p, c_p, c_int, c_p],
-    "aw_vq_onehot": [c_p, c_i64, c_int, c_p, c_p],
-    "aw_vq_gather": [c_p, c_p, c_i64, c_int, c_p, c_p],
-    "aw_patchify": [c_p, c_i64, c_int, c_int, c_int, c_p, c_i64, c_int, c_p],
-    "aw_weight_relayout": [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_i64, c_int, c_p],
-    "aw_weight_grad_scatter": [c_p, c_int, c_int, c_int, c_int, c_int, c_i64, c_p, c_p],
-    "aw_cast": [c_p, c_i64, c_p, c_int, c_p],
-    "aw_unpatch_head_fwd": [c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_p],
-    "aw_bn_finalize": [c_p, c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_int, c_p, c_p],
-    "aw_unpatch_head_bwd1": [c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "aw_unpatch_head_bwd2": [c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_int, c_p, c_int, c_p, c_p],
-    "aw_unpatch_head_fwd_ex": [c_p, c_int, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_p],
-    "aw_unpatch_head_bwd1_ex": [c_p, c_int, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "aw_unpatch_head_fwd_bwd1": [c_p, c_int, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                                 c_p, c_p, c_p, c_p],
-    "aw_unpatch_head_bwd2_ex": [c_p, c_int, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_int, c_p, c_int, c_p, c_p],
-    "aw_bn_group_stats": [c_p, c_i64, c_int, c_int, c_p, c_p],
-    "aw_bn_group_finalize": [c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_int, c_p, c_p],
-    "aw_bn_apply": [c_p, c_i64, c_int, c_int, c_p, c_int, c_p, c_f, ctypes.c_uint64, c_p, c_p, c_p, c_int, c_p],
-    "aw_bn_bwd_reduce": [c_p, c_i64, c_int, c_int, c_p, c_p, c_f, ctypes.c_uint64, c_p, c_p, c_p],
-    "aw_bn_bwd_apply": [c_p, c_i64, c_int, c_int, c_p, c_p, c_f, ctypes.c_uint64, c_p, c_p, c_i64, c_int, c_p, c_int,
-                        c_p, c_p, c_p],
-    "aw_mse_fwd": [c_p, c_p, c_i64, c_p, c_p],
-    "aw_mse_bwd": [c_p, c_p, c_i64, c_p, c_p, c_p],
-    "aw_scalar_add": [c_p, c_p, c_p, c_p],
-    "aw_mse_finalize": [c_p, c_i64, c_p, c_p],
-    "aw_mse_finalize_add": [c_p, c_i64, c_p, c_p, c_p, c_p],
-    "aw_radam_step": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_i64, c_i64, c_f, c_f, c_f, c_f, c_p, c_p,
-                      c_int, c_p],
-    "aw_radam_step_ops": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_i64, c_i64, c_f, c_f, c_f, c_f, c_p, c_p,
-                          c_p, c_int, c_p],
-    "aw_counter_add": [c_p, c_i64, c_p],
-    "aw_counter_add_snapshot": [c_p, c_i64, c_p, c_p],
-    "aw_counter_add_snapshot_zero": [c_p, c_i64, c_p, c_p, c_i64, c_p],
-    "aw_grad_norm_clip": [c_p, c_p, c_p, c_p, c_int, c_i64, c_f, c_p, c_p, c_p, c_p],
-    "aw_scale": [c_p, c_i64, c_p, c_p],
-    "aw_layernorm_fwd": [c_p, c_i64, c_int, c_p, c_p, c_f, c_p, c_int, c_p, c_p, c_p],
-    "aw_layernorm_bwd": [c_p, c_p, c_i64, c_int, c_p, c_p, c_p, c_p, c_int, c_p, c_p, c_p, c_int, c_f,
-                         ctypes.c_uint64, c_p, c_p],
-    "aw_class_head_fwd": [c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "aw_class_head_bwd": [c_p, c_p, c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "aw_embed_fwd": [c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_p],
-    "aw_embed_ln_fwd": [c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_int, c_p, c_p, c_p],
-    "aw_embed_bwd": [c_p, c_i64, c_int, c_int, c_p, c_p, c_p],
-    "aw_embed_bwd_sorted": [c_p, c_i64, c_int, c_int, c_int, c_p, c_p, c_p, c_p],
-    "aw_embed_sort": [c_p, c_i64, c_int, c_p, c_p],
-    "aw_embed_bwd_segsum": [c_p, c_int, c_int, c_p, c_p, c_p],
-    "aw_attn_fwd": [c_p, c_i64, c_int, c_int, c_int, c_int, c_p, c_p, c_p],
-    "aw_attn_bwd": [c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_p, c_p, c_p],
-    "aw_attn_fwd_dropout": [c_p, c_i64, c_int, c_int, c_int, c_int, c_p, c_p, c_f, ctypes.c_uint64, c_p, c_p],
-    "aw_attn_bwd_dropout": [c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_p, c_p, c_f, ctypes.c_uint64,
-                            c_p, c_p],
-    "aw_attn_decode": [c_p, c_i64, c_int, c_int, c_int, c_int, c_int, c_p, c_int, c_p, c_p],
-    "aw_ce_fwd": [c_p, c_i64, c_int, c_i64, c_p, c_int, c_p, c_p, c_p, c_p],
-    "aw_ce_bwd": [c_p, c_i64, c_int, c_i64, c_p, c_int, c_p, c_p, c_p, c_p, c_i64, c_int, c_p],
-    "aw_ce_finalize": [c_p, c_p, c_p, c_p],
-    "aw_vq_cluster_sums": [c_p, c_p, c_i64, c_int, c_int, c_p, c_p],
-    "aw_kmeans_update": [c_p, c_p, c_p, c_int, c_int, c_p, c_p],
-    "aw_rvq_ema_update": [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_f, c_f, c_f, ctypes.c_uint64, c_p, c_p,
-                          c_p],
-    "aw_rvq_residual": [c_p, c_p, c_i64, c_p, c_int, c_p, c_p],
-    "aw_rvq_backward": [c_p, c_p, c_p, c_p, c_int, c_i64, c_int, c_f, c_p, c_p],
-    "aw_gru_pack_weights": [c_p, c_int, c_int, c_p, c_p, c_p],
-    "aw_gru_step_fwd": [c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "aw_gru_bias_grad": [c_p, c_i64, c_int, c_p, c_p],
-    "aw_gru_step_bwd": [c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "aw_vq_decode_gather": [c_p, c_i64, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p, c_p, c_p],
-    "aw_sample_next": [c_p, c_int, c_int, c_int, c_int, c_f, c_int, ctypes.c_uint64, c_i64, c_p, c_i64, c_i64, c_p,
-                       c_p, c_p],
-    "aw_sample_next_ex": [ctypes.POINTER(SampleArgs), c_p],
-    "aw_beam_step": [ctypes.POINTER(BeamArgs), c_p],
-    "aw_beam_gather": [c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_int, c_int, c_int, c_int, c_p, c_p],
-    "aw_beam_backtrack": [c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_i64, c_i64, c_p, c_p, c_p],
-    "aw_score_rows": [c_p, c_i64, c_int, c_int, c_p, c_i64, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p],
-    "aw_window_sqerr": [c_p, c_p, c_p, c_i64, c_i64, c_int, c_int, c_p, c_p, c_p],
-    "aw_ensemble_stats": [ctypes.POINTER(EnsembleArgs), c_p],
-    "aw_knn_workspace": [c_i64, c_i64, c_int, c_int, c_int],
-    "aw_knn": [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_int, c_int, c_p, c_p, c_int, c_p, c_i64, c_p, c_p, c_p],
-    "aw_knn_describe": [ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)],
-}
-
-RET_I64 = {"aw_gemm_workspace", "aw_wgrad_batch_workspace", "aw_res_dropout_masks_bytes", "aw_knn_workspace"}
-
-_lib = None
 
 
 class NativeError(RuntimeError):
     pass
+
+
+_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32,
+            "float": ctypes.c_float, "double": ctypes.c_double}
+# <const> <type> <stars, each optionally const> <the rest: declarators or a parameter name>
+_DECL = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\b\s*)?)*)(.*)", re.S)
+_PREPROCESSOR_NOISE = re.compile(r"#\s*(?:ifndef\s+\w+|ifdef\s+\w+|endif|include\s*<[\w./]+>|define\s+\w+)")
+
+
+def parse_header(text: str):
+    """(constants, structs, prototypes) of a C header in the dialect of include/arcweld_amd.h.
+
+    constants: name -> int, from ``enum { NAME = n, ... };`` and ``#define NAME <integer>``;
+    structs: C name -> ctypes.Structure subclass, from ``typedef struct { ... } name;`` (scalars by type, every
+    pointer a c_void_p, ``T name[N]`` an array of N); prototypes: name -> (restype, argtypes), a pointer to one of the
+    header's structs as POINTER(that Structure), any other pointer as c_void_p.
+    Anything else -- an unknown type, declarator, directive or declaration -- raises NativeError naming it."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    constants, structs, prototypes, code, in_cpp = {}, {}, {}, [], False
+    for line in text.splitlines():
+        s = line.strip()
+        m = re.fullmatch(r"#\s*define\s+(\w+)\s+(-?(?:0[xX][0-9a-fA-F]+|\d+))", s)
+        if m:
+            constants[m.group(1)] = int(m.group(2), 0)
+        elif s.startswith("#"):
+            if not _PREPROCESSOR_NOISE.fullmatch(s):
+                raise NativeError(f"header: cannot read the directive `{s}`")
+            in_cpp = s.split() == ["#ifdef", "__cplusplus"]
+        elif not in_cpp:
+            code.append(line)
+        elif s not in ("", 'extern "C" {', "}"):    # a __cplusplus guard holds one of these two lines
+            raise NativeError(f"header: cannot read `{s}` inside #ifdef __cplusplus")
+    text = "\n".join(code)
+
+    def ctype(base, stars, what, pointee_structs=False):
+        if base not in _SCALARS and base not in structs and not (stars and base in ("void", "char")):
+            raise NativeError(f"header: unknown type `{base}` in `{what}`")
+        if not stars:
+            if base in structs:
+                raise NativeError(f"header: a struct by value in `{what}`")
+            return _SCALARS[base]
+        if pointee_structs and base in structs and stars.count("*") == 1:
+            return ctypes.POINTER(structs[base])
+        return ctypes.c_void_p
+
+    def fields(body, cname):
+        out = []
+        for decl in filter(None, (" ".join(d.split()) for d in body.split(";"))):
+            what = f"{decl}; of {cname}"
+            m = _DECL.fullmatch(decl)
+            if not m:
+                raise NativeError(f"header: cannot read `{what}`")
+            base, stars, rest = m.groups()
+            names = [d.strip() for d in rest.split(",")]
+            if stars and len(names) > 1:
+                raise NativeError(f"header: several declarators after a pointer type in `{what}`")
+            t = ctype(base, stars, what)
+            for d in names:
+                m = re.fullmatch(r"(\w+)(?:\s*\[\s*(\w+)\s*\])?", d)
+                if not m:
+                    raise NativeError(f"header: cannot read the declarator `{d}` in `{what}`")
+                name, dim = m.groups()
+                if dim is not None and not dim.isdigit() and dim not in constants:
+                    raise NativeError(f"header: array size `{dim}` is not defined in `{what}`")
+                out.append((name, t if dim is None else t * (int(dim) if dim.isdigit() else constants[dim])))
+        return out
+
+    pos = 0
+    item = re.compile(r"\s*(?:enum\s*\{(?P<enum>[^{}]*)\}\s*;"
+                      r"|typedef\s+struct\s*\{(?P<body>[^{}]*)\}\s*(?P<struct>\w+)\s*;"
+                      r"|(?P<ret>[^;{}()]+?)\b(?P<fn>\w+)\s*\((?P<params>[^;{}()]*)\)\s*;)")
+    while text[pos:].strip():
+        m = item.match(text, pos)
+        if not m:
+            raise NativeError("header: cannot read the declaration `"
+                              + " ".join(text[pos:].split(";")[0].split()) + "`")
+        pos = m.end()
+        if m.group("enum") is not None:
+            for member in filter(None, (e.strip() for e in m.group("enum").split(","))):
+                mm = re.fullmatch(r"(\w+)\s*=\s*(-?\d+)", member)
+                if not mm:
+                    raise NativeError(f"header: cannot read the enum member `{member}`")
+                constants[mm.group(1)] = int(mm.group(2))
+        elif m.group("struct") is not None:
+            cname = m.group("struct")
+            structs[cname] = type(cname, (ctypes.Structure,), {"_fields_": fields(m.group("body"), cname),
+                                                               "__doc__": f"{cname} (include/arcweld_amd.h)"})
+        else:
+            fn = m.group("fn")
+            what = " ".join(m.group(0).split())
+            rm = _DECL.fullmatch(m.group("ret").strip())
+            if not rm or rm.group(3).strip():
+                raise NativeError(f"header: cannot read the return type of `{what}`")
+            base, stars = rm.group(1), rm.group(2)
+            restype = ctypes.c_char_p if (base, stars.count("*")) == ("char", 1) else ctype(base, stars, what)
+            argtypes = []
+            params = m.group("params").strip()
+            for p in ([] if params == "void" else params.split(",")):
+                pm = _DECL.fullmatch(p.strip())
+                if not pm or not re.fullmatch(r"\w*", pm.group(3).strip()):
+                    raise NativeError(f"header: cannot read the parameter `{p.strip()}` of `{what}`")
+                argtypes.append(ctype(pm.group(1), pm.group(2), what, pointee_structs=True))
+            prototypes[fn] = (restype, argtypes)
+    return constants, structs, prototypes
+
+
+def _read_header():
+    try:
+        with open(HEADER) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise NativeError(f"the C ABI header {HEADER} cannot be read: {e}") from e
+
+
+_CONSTANTS, _STRUCTS, _PROTOTYPES = _read_header()
+globals().update(_CONSTANTS)        # AW_F32, AW_RES_CHAIN_MAX, AW_ABI_VERSION, ...: every header constant, by its name
+# the short names that tests/ compare with the header's text: the header's values under another name, not copies
+OPS_PER_SEG, BEAM_MAX_W = _CONSTANTS["AW_OPS_PER_SEG"], _CONSTANTS["AW_BEAM_MAX_W"]
+KNN_MAX_K, KNN_MAX_SPLITS = _CONSTANTS["AW_KNN_MAX_K"], _CONSTANTS["AW_KNN_MAX_SPLITS"]
+
+GemmArgs = _STRUCTS["aw_gemm_args"]
+RelayoutJob = _STRUCTS["aw_relayout_job"]
+OperandDesc = _STRUCTS["aw_operand_desc"]
+ResChainFwdArgs = _STRUCTS["aw_res_chain_fwd_args"]
+ResChainBwdArgs = _STRUCTS["aw_res_chain_bwd_args"]
+SampleArgs = _STRUCTS["aw_sample_args"]
+BeamArgs = _STRUCTS["aw_beam_args"]
+EnsembleArgs = _STRUCTS["aw_ensemble_args"]
+
+# name -> argtypes of every prototype the header declares
+SIGNATURES = {name: argtypes for name, (_, argtypes) in _PROTOTYPES.items()}
+
+_lib = None
 
 
 def load(path: str = LIB_PATH):
@@ -266,12 +168,15 @@ def load(path: str = LIB_PATH):
         raise NativeError(f"HIP library not built: {path} is missing (run `python -c 'import __graft_entry__ as g; "
                           f"g.build()'` or `make -C vq-vae-transformer-arc-welding_amd/csrc`)")
     lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
-    lib.aw_last_error.restype = ctypes.c_char_p
-    lib.aw_last_error.argtypes = []
-    for name, argtypes in SIGNATURES.items():
+    lib.aw_version.restype, lib.aw_version.argtypes = _PROTOTYPES["aw_version"]
+    # entry points keep their names across ABI versions while their parameter lists change: a stale build would be
+    # called with the wrong arguments, so it is refused before anything else is looked up
+    if lib.aw_version() != AW_ABI_VERSION:  # noqa: F821  (a header constant)
+        raise NativeError(f"{path} reports C ABI version {lib.aw_version()}, include/arcweld_amd.h declares "
+                          f"{AW_ABI_VERSION}: rebuild the library from this tree")  # noqa: F821
+    for name, (restype, argtypes) in _PROTOTYPES.items():
         fn = getattr(lib, name)
-        fn.restype = c_i64 if name in RET_I64 else c_int
-        fn.argtypes = argtypes
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -299,7 +204,7 @@ def ptr(t):
 
 def dtype_code(dt: torch.dtype) -> int:
     if dt == torch.float32:
-        return AW_F32
+        return AW_F32  # noqa: F821
     if dt == torch.bfloat16:
-        return AW_BF16
+        return AW_BF16  # noqa: F821
     raise NativeError(f"unsupported operand dtype {dt}")

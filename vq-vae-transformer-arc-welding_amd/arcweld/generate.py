@@ -125,12 +125,12 @@ def forecast_cycles(vqvae, decoder, x_prompt, n_cycles, num_samples, quantiles=(
                          f"got {tuple(getattr(x_prompt, 'shape', ()))}")
     from . import kernels as K
     N = int(num_samples)
-    if not 1 <= N <= K.nat.BEAM_MAX_W:
-        raise ValueError(f"forecast_cycles: num_samples = {num_samples} outside 1..{K.nat.BEAM_MAX_W}")
+    if not 1 <= N <= K.nat.AW_BEAM_MAX_W:
+        raise ValueError(f"forecast_cycles: num_samples = {num_samples} outside 1..{K.nat.AW_BEAM_MAX_W}")
     qs = [float(q) for q in quantiles]
     Q = len(qs)
-    if Q > K.nat.ENSEMBLE_MAX_Q or any(not 0.0 <= q <= 1.0 for q in qs) or any(a > b for a, b in zip(qs, qs[1:])):
-        raise ValueError(f"forecast_cycles: quantiles must be at most {K.nat.ENSEMBLE_MAX_Q} ascending probabilities "
+    if Q > K.nat.AW_ENSEMBLE_MAX_Q or any(not 0.0 <= q <= 1.0 for q in qs) or any(a > b for a, b in zip(qs, qs[1:])):
+        raise ValueError(f"forecast_cycles: quantiles must be at most {K.nat.AW_ENSEMBLE_MAX_Q} ascending probabilities "
                          f"in [0, 1], got {tuple(quantiles)}")
     B, C = x_prompt.shape[0], x_prompt.shape[2]
     c = x_prompt.shape[1] // L

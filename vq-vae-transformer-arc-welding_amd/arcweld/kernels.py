@@ -151,7 +151,7 @@ def gemm(A, B, M, N, K, *, stream=None, flops=None, **kw):
     return kw.get("C")
 
 
-MAX_GROUPS = 16
+MAX_GROUPS = nat.AW_GEMM_MAX_GROUPS
 
 
 def gemm_grouped(problems, stream=None):
@@ -172,7 +172,7 @@ def gemm_grouped(problems, stream=None):
         _timed(s, lambda sp: call("aw_gemm_grouped", arr, len(chunk), sp), fl, _gemm_tag(chunk[0][0]), nm)
 
 
-WGRAD_BATCH_MAX = 32     # aw_wgrad_batch problems per launch (include/arcweld_amd.h AW_WGRAD_BATCH_MAX)
+WGRAD_BATCH_MAX = nat.AW_WGRAD_BATCH_MAX     # aw_wgrad_batch problems per launch
 
 
 def wgrad_batch_ok(problems):
@@ -231,7 +231,7 @@ def wgrad_issue(problems, stream=None):
 
 
 # ------------------------------------------------------------------------------------------------ encoder chain
-RES_CHAIN_MAX = nat.RES_CHAIN_MAX
+RES_CHAIN_MAX = nat.AW_RES_CHAIN_MAX
 
 
 def res_chain_ok(H, R, T, RT, taps=1, seg=16, which="ENC"):
@@ -363,8 +363,8 @@ def res_chain_fwd(a0, x0, w1, w2, b1, b2, dh, a1, dx, a, drop=(0.0, None), seed_
     if tail is not None:
         wt, tb, Y, cst = tail
         k1 = len(wt)
-        if taps != 3 or not (1 <= k1 <= nat.RES_TAIL_MAX):
-            raise nat.NativeError(f"res_chain_fwd: the tail needs taps == 3 and 1..{nat.RES_TAIL_MAX} matrices")
+        if taps != 3 or not (1 <= k1 <= nat.AW_RES_TAIL_MAX):
+            raise nat.NativeError(f"res_chain_fwd: the tail needs taps == 3 and 1..{nat.AW_RES_TAIL_MAX} matrices")
         if Y.dtype != torch.bfloat16 or tuple(Y.shape) != (N, k1 * H) or not Y.is_contiguous():
             raise nat.NativeError(f"res_chain_fwd: tail Y must be a contiguous ({N}, {k1 * H}) bfloat16 tensor")
         if tb.dtype != torch.float32 or tb.numel() != H or not tb.is_contiguous():
@@ -462,7 +462,7 @@ def res_pack_weights(src, fwd=None, bwd=None, taps=1, stream=None, job_taps=None
     """Fragment-packed copies of [512][taps*512] bf16 [out][(tap, in)] weights for the chain (aw_res_pack_weights):
     fwd[i] <- W packed (aw_res_chain_fwd's w1 / w2), bwd[i] <- the backward operand packed (aw_res_chain_bwd's w1t /
     w2t); either list may be None.  One launch per 32 matrices.  job_taps[i] (default taps) may be 1 in a taps = 3
-    launch: a [512][512] matrix, forward copy only (the chain tail's matrices, aw_res_pack_weights_mixed)."""
+    launch: a [512][512] matrix, forward copy only (the chain tail's matrices)."""
     n = len(src)
     fwd = fwd if fwd is not None else [None] * n
     bwd = bwd if bwd is not None else [None] * n
@@ -473,15 +473,12 @@ def res_pack_weights(src, fwd=None, bwd=None, taps=1, stream=None, job_taps=None
         for t in (src[i], fwd[i], bwd[i]):
             if t is not None and (t.dtype != torch.bfloat16 or t.numel() != 512 * 512 * jt[i] or not t.is_contiguous()):
                 raise nat.NativeError(f"res_pack_weights: need contiguous 512 x {512 * jt[i]} bfloat16 tensors")
-    for c0 in range(0, n, nat.RES_PACK_MAX):
-        sl = slice(c0, c0 + nat.RES_PACK_MAX)
+    for c0 in range(0, n, nat.AW_RES_PACK_MAX):
+        sl = slice(c0, c0 + nat.AW_RES_PACK_MAX)
         m = len(src[sl])
         arr = lambda ts: (ctypes.c_void_p * m)(*[ptr(t) for t in ts])  # noqa: E731
-        if job_taps is None:
-            call("aw_res_pack_weights", arr(src[sl]), arr(fwd[sl]), arr(bwd[sl]), m, int(taps), stream_ptr(stream))
-        else:
-            call("aw_res_pack_weights_mixed", arr(src[sl]), arr(fwd[sl]), arr(bwd[sl]), (ctypes.c_int * m)(*jt[sl]), m,
-                 int(taps), stream_ptr(stream))
+        call("aw_res_pack_weights", arr(src[sl]), arr(fwd[sl]), arr(bwd[sl]),
+             (ctypes.c_int * m)(*jt[sl]) if job_taps is not None else None, m, int(taps), stream_ptr(stream))
 
 
 # ------------------------------------------------------------------------------------------------ VQ
@@ -496,7 +493,7 @@ def _chk_vq(who, name, t, shape, dtypes=(torch.float32,)):
 
 def vq_forward(z2d, E, zq, idx, counts, sqerr, stream=None, zq_copy=None, count_groups=1):
     """zq_copy: optional bf16/f32 tensor that also receives z_q.  count_groups > 1: counts holds that many partial
-    histograms of K floats (aw_vq_forward_ex2; vq_finalize sums them)."""
+    histograms of K floats (vq_finalize sums them)."""
     if z2d.dim() != 2 or E.dim() != 2:
         raise nat.NativeError(f"vq_forward: z must be (N, D) and E (K, D) (got {tuple(z2d.shape)}, {tuple(E.shape)})")
     N, D = z2d.shape
@@ -512,7 +509,7 @@ def vq_forward(z2d, E, zq, idx, counts, sqerr, stream=None, zq_copy=None, count_
         raise nat.NativeError(f"vq_forward: counts must hold count_groups x K = {count_groups} x {Kc} contiguous "
                               f"float32 values (got {str(counts.dtype).replace('torch.', '')} {tuple(counts.shape)})")
     _maybe_timed(stream, "vq_fwd", 2.0 * N * Kc * D, lambda sp: call(
-        "aw_vq_forward_ex2", ptr(z2d), ptr(E), N, Kc, D, ptr(zq), ptr(idx), ptr(counts), int(count_groups),
+        "aw_vq_forward", ptr(z2d), ptr(E), N, Kc, D, ptr(zq), ptr(idx), ptr(counts), int(count_groups),
         ptr(sqerr), ptr(zq_copy), dtype_code(zq_copy.dtype) if zq_copy is not None else 0, sp),
         # the pinned kernel (codebook in LDS, f32-input MFMA) serves K <= 512, D in {16, 32, 64} (csrc/vq.hip)
         lambda: ("vq_fwd_pinned_kernel" if Kc <= 512 and D in (16, 32, 64) else "vq_fwd_kernel",
@@ -520,12 +517,12 @@ def vq_forward(z2d, E, zq, idx, counts, sqerr, stream=None, zq_copy=None, count_
 
 
 def vq_finalize(counts, sqerr, N, K, D, beta, loss, perplexity, stream=None, count_groups=1):
-    call("aw_vq_finalize_ex", ptr(counts), int(count_groups), ptr(sqerr), N, K, D, float(beta), ptr(loss),
+    call("aw_vq_finalize", ptr(counts), int(count_groups), ptr(sqerr), N, K, D, float(beta), ptr(loss),
          ptr(perplexity), stream_ptr(stream))
 
 
 def vq_backward(z2d, E, idx, g_zq, g_loss, beta, dz, dE, stream=None, dz_copy=None):
-    """dz_copy: optional bf16/f32 tensor that also receives dz (aw_vq_backward_ex)."""
+    """dz_copy: optional bf16/f32 tensor that also receives dz."""
     if z2d.dim() != 2 or E.dim() != 2:
         raise nat.NativeError(f"vq_backward: z must be (N, D) and E (K, D) (got {tuple(z2d.shape)}, {tuple(E.shape)})")
     N, D = z2d.shape
@@ -540,12 +537,9 @@ def vq_backward(z2d, E, idx, g_zq, g_loss, beta, dz, dE, stream=None, dz_copy=No
     _chk_vq("vq_backward", "dE", dE, (E.shape[0], D))
     if dz_copy is not None:
         _chk_vq("vq_backward", "dz_copy", dz_copy, (N, D), (torch.float32, torch.bfloat16))
-    if dz_copy is None:
-        call("aw_vq_backward", ptr(z2d), ptr(E), ptr(idx), ptr(g_zq), ptr(g_loss), N, E.shape[0], D, float(beta),
-             ptr(dz), ptr(dE), stream_ptr(stream))
-    else:
-        call("aw_vq_backward_ex", ptr(z2d), ptr(E), ptr(idx), ptr(g_zq), ptr(g_loss), N, E.shape[0], D, float(beta),
-             ptr(dz), ptr(dE), ptr(dz_copy), dtype_code(dz_copy.dtype), stream_ptr(stream))
+    call("aw_vq_backward", ptr(z2d), ptr(E), ptr(idx), ptr(g_zq), ptr(g_loss), N, E.shape[0], D, float(beta),
+         ptr(dz), ptr(dE), ptr(dz_copy), dtype_code(dz_copy.dtype) if dz_copy is not None else AW_F32,
+         stream_ptr(stream))
 
 
 # ------------------------------------------------------------------------ residual VQ (EMA codebooks)
@@ -821,9 +815,9 @@ def ensemble_stats(x, q, mean=None, std=None, quant=None, y=None, seg=None, crps
         raise nat.NativeError("ensemble_stats: bad_count must be one int32 on the device")
     _chk_i32_counter(bad_count, "ensemble_stats")
     a = nat.EnsembleArgs()
-    qa = (nat.c_f * max(Q, 1))(*qs)
+    qa = (ctypes.c_float * max(Q, 1))(*qs)        # a host array: it outlives the call below
     a.x, a.G, a.N, a.M = ptr(x), G, N, M
-    a.q, a.Q = ctypes.cast(qa, ctypes.POINTER(nat.c_f)), Q
+    a.q, a.Q = ctypes.cast(qa, ctypes.c_void_p), Q
     a.mean, a.std, a.quant, a.y = ptr(mean), ptr(std), ptr(quant), ptr(y)
     a.seg, a.crps, a.cover, a.bad_count = seg, ptr(crps), ptr(cover), ptr(bad_count)
     call("aw_ensemble_stats", ctypes.byref(a), stream_ptr(stream))
@@ -831,7 +825,7 @@ def ensemble_stats(x, q, mean=None, std=None, quant=None, y=None, seg=None, crps
 
 def knn_describe():
     """aw_knn_describe: (tile_q, tile_x, chunk_d, max_k) of the k-NN kernel (the tests aim at the tile edges)."""
-    v = [nat.c_int(0) for _ in range(4)]
+    v = [ctypes.c_int(0) for _ in range(4)]
     call("aw_knn_describe", *[ctypes.byref(c) for c in v])
     return tuple(int(c.value) for c in v)
 
@@ -888,7 +882,7 @@ def weight_relayout(W, O, I, k, tap, mode, out, ldo=0, stream=None):
     call("aw_weight_relayout", ptr(W), O, I, k, tap, mode, ptr(out), ldo, dtype_code(out.dtype), stream_ptr(stream))
 
 
-RELAYOUT_MAX_JOBS = 40
+RELAYOUT_MAX_JOBS = nat.AW_RELAYOUT_MAX_JOBS
 
 
 def _dense(W, who):
@@ -931,19 +925,19 @@ def bn_finalize(colstats, n, H, gamma, beta, rm, rv, nbt, eps, momentum, trainin
 def unpatch_head_fwd(y, Q, stats, w2, b2, x_hat, stream=None):
     """y (R, H) f32 or bf16 (the ConvT output in the bf16 operand mode)."""
     R, H = y.shape
-    call("aw_unpatch_head_fwd_ex", ptr(y), dtype_code(y.dtype), R, H, Q, ptr(stats), ptr(w2), ptr(b2), ptr(x_hat),
+    call("aw_unpatch_head_fwd", ptr(y), dtype_code(y.dtype), R, H, Q, ptr(stats), ptr(w2), ptr(b2), ptr(x_hat),
          stream_ptr(stream))
 
 
 def unpatch_head_bwd1(y, Q, stats, w2, g_xhat, gsums, gw2, gb2, ggamma, gbeta, stream=None):
     R, H = y.shape
-    call("aw_unpatch_head_bwd1_ex", ptr(y), dtype_code(y.dtype), R, H, Q, ptr(stats), ptr(w2), ptr(g_xhat), ptr(gsums),
+    call("aw_unpatch_head_bwd1", ptr(y), dtype_code(y.dtype), R, H, Q, ptr(stats), ptr(w2), ptr(g_xhat), ptr(gsums),
          ptr(gw2), ptr(gb2), ptr(ggamma), ptr(gbeta), stream_ptr(stream))
 
 
 def unpatch_head_bwd2(y, Q, stats, w2, g_xhat, gsums, training, g_y, db_y, stream=None):
     R, H = y.shape
-    call("aw_unpatch_head_bwd2_ex", ptr(y), dtype_code(y.dtype), R, H, Q, ptr(stats), ptr(w2), ptr(g_xhat),
+    call("aw_unpatch_head_bwd2", ptr(y), dtype_code(y.dtype), R, H, Q, ptr(stats), ptr(w2), ptr(g_xhat),
          ptr(gsums), int(training), ptr(g_y), dtype_code(g_y.dtype), ptr(db_y), stream_ptr(stream))
 
 
@@ -963,7 +957,7 @@ def unpatch_head_fwd_bwd1(y, Q, stats, w2, b2, x, gscale, x_hat, g_xhat, sqerr, 
 
 
 def head_bf16_ok(H):
-    """The head passes take a bf16 ConvT output when H is a power of two in 64..2048 (aw_unpatch_head_*_ex)."""
+    """The head passes take a bf16 ConvT output when H is a power of two in 64..2048 (aw_unpatch_head_*)."""
     return 64 <= H <= 2048 and H & (H - 1) == 0
 
 
@@ -991,35 +985,30 @@ def mse_finalize_add(sqerr, numel, addend, out, total, stream=None):
 # ------------------------------------------------------------------------------------------ optimizer
 def radam_step(param, grad, m, v, seg_off, seg_len, seg_wd, seg_active, nseg, total, step, lr, beta1, beta2, eps,
                gscale=None, stream=None, step_ptr=None, ops=None, zero_grad=False):
-    """aw_radam_step, or aw_radam_step_ops when `ops` (device table of aw_operand_desc, AW_OPS_PER_SEG per
-    segment) is given: the update also writes the operand copies of the updated weights.  zero_grad: the updated
-    elements' gradients are zeroed in the same pass."""
-    args = (ptr(param), ptr(grad), ptr(m), ptr(v), ptr(seg_off), ptr(seg_len), ptr(seg_wd), ptr(seg_active), int(nseg),
-            int(total), int(step), float(lr), float(beta1), float(beta2), float(eps), ptr(gscale), ptr(step_ptr))
-    if ops is None:
-        call("aw_radam_step", *args, int(bool(zero_grad)), stream_ptr(stream))
-    else:
-        call("aw_radam_step_ops", *args, ptr(ops), int(bool(zero_grad)), stream_ptr(stream))
+    """aw_radam_step; with `ops` (device table of aw_operand_desc, AW_OPS_PER_SEG per segment) the update also
+    writes the operand copies of the updated weights.  zero_grad: the updated elements' gradients are zeroed in the
+    same pass."""
+    call("aw_radam_step", ptr(param), ptr(grad), ptr(m), ptr(v), ptr(seg_off), ptr(seg_len), ptr(seg_wd),
+         ptr(seg_active), int(nseg), int(total), int(step), float(lr), float(beta1), float(beta2), float(eps),
+         ptr(gscale), ptr(step_ptr), ctypes.cast(ptr(ops), ctypes.POINTER(nat.OperandDesc)), int(bool(zero_grad)),
+         stream_ptr(stream))
 
 
 def counter_add_snapshot(counter, snapshot, v=1, stream=None, zero=None):
     """counter += v and snapshot = the new value, in one launch; `zero` (a contiguous float64 tensor) is zeroed by
     the same launch."""
-    if zero is None:
-        call("aw_counter_add_snapshot", ptr(counter), int(v), ptr(snapshot), stream_ptr(stream))
-        return
-    if zero.dtype != torch.float64 or not zero.is_contiguous():
+    if zero is not None and (zero.dtype != torch.float64 or not zero.is_contiguous()):
         raise nat.NativeError("counter_add_snapshot: zero must be a contiguous float64 tensor")
-    call("aw_counter_add_snapshot_zero", ptr(counter), int(v), ptr(snapshot), ptr(zero), zero.numel(),
+    call("aw_counter_add", ptr(counter), int(v), ptr(snapshot), ptr(zero), zero.numel() if zero is not None else 0,
          stream_ptr(stream))
 
 
 def counter_add(counter, v=1, stream=None):
     """counter (int64 device tensor) += v on the stream (per-step RNG / optimizer-step counters)."""
-    call("aw_counter_add", ptr(counter), int(v), stream_ptr(stream))
+    call("aw_counter_add", ptr(counter), int(v), None, None, 0, stream_ptr(stream))
 
 
-NORM_WS = 1024      # AW_NORM_WS
+NORM_WS = nat.AW_NORM_WS
 
 
 def grad_norm_clip(grad, seg_off, seg_len, seg_active, nseg, max_norm, ws, out_norm, out_coef, stream=None):
@@ -1111,28 +1100,25 @@ def _maybe_timed(stream, tag, flops, fn, info=None):
     _timed(s, fn, flops, tag, *(info() if info is not None else ()))
 
 
-def attn_fwd(qkv, B, T, n_head, d, y, lse, drop=(0.0, 0), seed_ptr=None, stream=None):
-    """drop = (p, seed): attention-probability dropout (aw_attn_fwd_dropout); p = 0 is plain aw_attn_fwd."""
+def _attn_drop(drop, seed_ptr):
+    """(drop_p, drop_seed, seed_ptr) of the attention entry points; no dropout passes neither seed."""
     if drop[0] > 0:
-        _maybe_timed(stream, "attn_fwd", attn_flops(B, T, n_head, d), lambda sp: call(
-            "aw_attn_fwd_dropout", ptr(qkv), B, T, n_head, d, dtype_code(qkv.dtype), ptr(y), ptr(lse),
-            float(drop[0]), int(drop[1]) & 0xFFFFFFFFFFFFFFFF, ptr(seed_ptr), sp))
-        return
+        return float(drop[0]), int(drop[1]) & 0xFFFFFFFFFFFFFFFF, ptr(seed_ptr)
+    return 0.0, 0, None
+
+
+def attn_fwd(qkv, B, T, n_head, d, y, lse, drop=(0.0, 0), seed_ptr=None, stream=None):
+    """drop = (p, seed): attention-probability dropout; p = 0 is none."""
     _maybe_timed(stream, "attn_fwd", attn_flops(B, T, n_head, d), lambda sp: call(
-        "aw_attn_fwd", ptr(qkv), B, T, n_head, d, dtype_code(qkv.dtype), ptr(y), ptr(lse), sp))
+        "aw_attn_fwd", ptr(qkv), B, T, n_head, d, dtype_code(qkv.dtype), ptr(y), ptr(lse), *_attn_drop(drop, seed_ptr),
+        sp))
 
 
 def attn_bwd(qkv, y, dy, lse, B, T, n_head, d, dqkv, ws, drop=(0.0, 0), seed_ptr=None, stream=None):
     """Algorithmic FLOPs: twice the forward (dQ, dK, dV, dP; the recomputed S is not counted)."""
-    fl = 2.0 * attn_flops(B, T, n_head, d)
-    if drop[0] > 0:
-        _maybe_timed(stream, "attn_bwd", fl, lambda sp: call(
-            "aw_attn_bwd_dropout", ptr(qkv), ptr(y), ptr(dy), ptr(lse), B, T, n_head, d, dtype_code(qkv.dtype),
-            ptr(dqkv), ptr(ws), float(drop[0]), int(drop[1]) & 0xFFFFFFFFFFFFFFFF, ptr(seed_ptr), sp))
-        return
-    _maybe_timed(stream, "attn_bwd", fl, lambda sp: call(
+    _maybe_timed(stream, "attn_bwd", 2.0 * attn_flops(B, T, n_head, d), lambda sp: call(
         "aw_attn_bwd", ptr(qkv), ptr(y), ptr(dy), ptr(lse), B, T, n_head, d, dtype_code(qkv.dtype), ptr(dqkv),
-        ptr(ws), sp))
+        ptr(ws), *_attn_drop(drop, seed_ptr), sp))
 
 
 # ------------------------------------------------------------------------------ ResBlock BatchNorm

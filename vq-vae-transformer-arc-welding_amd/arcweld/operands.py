@@ -7,7 +7,7 @@ a decoder conv as [O][3I] (forward) and [3O][I] (input gradient), the ConvT as [
 * refreshes them with ONE aw_weight_relayout_batch launch when a weight changed outside the optimizer (signature:
   data_ptr and version counter of every source parameter -- load_state_dict, .to(), manual edits), and
 * otherwise leaves them alone when the flat RAdam maintains them (arcweld.optim.RAdam.attach_operands): its update
-  kernel writes the cast copy of every updated element (aw_radam_step_ops), so a training step has no relayout
+  kernel writes the cast copy of every updated element (aw_radam_step with ops), so a training step has no relayout
   launch at all.
 
 A set that no optimizer maintains is refreshed on every use (the safe default).

@@ -210,7 +210,7 @@ class RAdam(torch.optim.Optimizer):
 
     def attach_operands(self, opset):
         """Keep the GEMM operand copies of ``opset`` (arcweld.operands.OperandSet) current from the update kernel
-        (aw_radam_step_ops): each updated element is also cast into the copies of its parameter, so the step needs no
+        (aw_radam_step with ops): each updated element is also cast into the copies of its parameter, so the step needs no
         relayout launch.  Returns False (and leaves the set refreshed per forward) when a copy's parameter is not in
         this optimizer or one parameter feeds more than AW_OPS_PER_SEG copies."""
         import ctypes
@@ -224,12 +224,12 @@ class RAdam(torch.optim.Optimizer):
             if i is None:
                 return False
             per[i].append(j)
-        if any(len(x) > nat.OPS_PER_SEG for x in per):
+        if any(len(x) > nat.AW_OPS_PER_SEG for x in per):
             return False
-        table = (nat.OperandDesc * (nat.OPS_PER_SEG * len(per)))()
+        table = (nat.OperandDesc * (nat.AW_OPS_PER_SEG * len(per)))()
         for i, js in enumerate(per):
-            for k in range(nat.OPS_PER_SEG):
-                d = table[nat.OPS_PER_SEG * i + k]
+            for k in range(nat.AW_OPS_PER_SEG):
+                d = table[nat.AW_OPS_PER_SEG * i + k]
                 if k >= len(js):
                     d.mode = -1
                     continue

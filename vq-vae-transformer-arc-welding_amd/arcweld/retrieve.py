@@ -20,7 +20,7 @@ from . import _native as nat
 
 __all__ = ["knn_search", "knn_vote", "latent_knn_probe", "standard_scaler", "MAX_K"]
 
-MAX_K = nat.KNN_MAX_K
+MAX_K = nat.AW_KNN_MAX_K
 _ROWS_PER_CHUNK = 8192
 
 

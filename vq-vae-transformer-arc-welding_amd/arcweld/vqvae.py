@@ -53,7 +53,7 @@ def rng_snapshot(m, dev, p_drop, zero=None):
     return snap
 
 
-# partial code histograms of the VQ forward (aw_vq_forward_ex2): workgroup b adds into partial b % 8, so no more
+# partial code histograms of the VQ forward (aw_vq_forward, count_groups): workgroup b adds into partial b % 8, so no more
 # than N / (64 * 8) workgroups add into one address (at 1, every workgroup's adds into the same 2 KB serialised at
 # the memory-side atomic units: 2.5 us of the configs[1] kernel)
 VQ_COUNT_GROUPS = 8
@@ -63,7 +63,7 @@ def accumulators(m, dev, K, H, zero=True):
     """Device accumulators of one forward, carved from one persistent f64 block (zeroed by ONE launch: here, or by
     rng_snapshot's when zero=False and the caller passes it the "block"): VQ sqerr (f64), MSE sqerr (f64,
     fused_train_step), BN column statistics (2H f64) and the VQ code counts (VQ_COUNT_GROUPS partial histograms of K
-    f32, summed by aw_vq_finalize_ex).  Each is consumed inside the call that filled it (never across a
+    f32, summed by aw_vq_finalize).  Each is consumed inside the call that filled it (never across a
     forward/backward boundary)."""
     key = (dev, K, H)
     st = m.__dict__.get("_acc_block")
@@ -137,7 +137,7 @@ def routes(m, sh, T):
     rt.bf_y = T != F32 and K.head_bf16_ok(H) and os.environ.get("ARCWELD_HEAD_BF16", "1") == "1"
     # The un-patch ConvT rides as the tail of the decoder chain launch when that runs and Y is bf16: x_R is still in
     # LDS there, so the ConvT is k1 more 1-tap convs and no launch of its own (ARCWELD_CONVT_TAIL=0: a GEMM)
-    rt.convt_tail = rt.dec_chain and rt.bf_y and k1 <= nat.RES_TAIL_MAX and K.convt_tail_ok()
+    rt.convt_tail = rt.dec_chain and rt.bf_y and k1 <= nat.AW_RES_TAIL_MAX and K.convt_tail_ok()
     # ... and the 1x1 conv (D = 64) as its head: the launch loads its rows of zq_T and writes y0 / ya0 itself
     # (ARCWELD_CHAIN_HEAD=0: a GEMM)
     rt.dec_head = rt.dec_chain and D == 64 and K.chain_head_ok()

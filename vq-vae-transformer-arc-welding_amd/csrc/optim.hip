@@ -375,74 +375,48 @@ __global__ void scale_kernel(float* x, int64_t n, const float* s) {
 extern "C" int aw_radam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq,
                              const int64_t* seg_off, const int64_t* seg_len, const float* seg_wd, const int* seg_active,
                              int nseg, int64_t total, int64_t step, float lr, float beta1, float beta2, float eps,
-                             const float* gscale, const int64_t* step_ptr, int zero_grad, void* stream) {
+                             const float* gscale, const int64_t* step_ptr, const aw_operand_desc* ops, int zero_grad,
+                             void* stream) {
   AW_REQUIRE(param && grad && exp_avg && exp_avg_sq && seg_off && seg_len && seg_wd && seg_active,
              "aw_radam_step: null pointer");
   AW_REQUIRE(nseg > 0 && nseg <= MAXSEG_LDS, "aw_radam_step: nseg must be in [1, %d]", MAXSEG_LDS);
   AW_REQUIRE((step_ptr || step >= 1) && total >= 0, "aw_radam_step: step counts from 1");
-  // scalars in double, as torch's _single_tensor_radam computes them (python floats); on the device when the
-  // step number lives there
-  const RAdamScalars S = radam_scalars(step_ptr ? 1 : step, lr, beta1, beta2, eps);
+  AW_REQUIRE(!ops || total < ((int64_t)1 << 31), "aw_radam_step: total must be < 2^31 elements");
   AW_REQUIRE(total % 4 == 0 && ((uintptr_t)param & 15) == 0 && ((uintptr_t)grad & 15) == 0 &&
                  ((uintptr_t)exp_avg & 15) == 0 && ((uintptr_t)exp_avg_sq & 15) == 0,
              "aw_radam_step: flat buffers must be 16-B aligned with total %% 4 == 0");
-  if (total == 0) return AW_OK;
-  int64_t g = (total / 4 + 255) / 256;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  hipLaunchKernelGGL(radam_kernel, dim3((int)g), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), param, grad,
-                     exp_avg, exp_avg_sq, seg_off, seg_len, seg_wd, seg_active, nseg, total, S, gscale, step_ptr,
-                     zero_grad);
-  return aw::check_launch("aw_radam_step");
-}
-
-extern "C" int aw_radam_step_ops(float* param, float* grad, float* exp_avg, float* exp_avg_sq,
-                                 const int64_t* seg_off, const int64_t* seg_len, const float* seg_wd,
-                                 const int* seg_active, int nseg, int64_t total, int64_t step, float lr, float beta1,
-                                 float beta2, float eps, const float* gscale, const int64_t* step_ptr,
-                                 const aw_operand_desc* ops, int zero_grad, void* stream) {
-  AW_REQUIRE(param && grad && exp_avg && exp_avg_sq && seg_off && seg_len && seg_wd && seg_active && ops,
-             "aw_radam_step_ops: null pointer");
-  AW_REQUIRE(nseg > 0 && nseg <= MAXSEG_LDS, "aw_radam_step_ops: nseg must be in [1, %d]", MAXSEG_LDS);
-  AW_REQUIRE((step_ptr || step >= 1) && total >= 0, "aw_radam_step_ops: step counts from 1");
-  AW_REQUIRE(total < ((int64_t)1 << 31), "aw_radam_step_ops: total must be < 2^31 elements");
-  AW_REQUIRE(total % 4 == 0 && ((uintptr_t)param & 15) == 0 && ((uintptr_t)grad & 15) == 0 &&
-                 ((uintptr_t)exp_avg & 15) == 0 && ((uintptr_t)exp_avg_sq & 15) == 0,
-             "aw_radam_step_ops: flat buffers must be 16-B aligned with total %% 4 == 0");
+  // scalars in double, as torch's _single_tensor_radam computes them (python floats); on the device when the
+  // step number lives there
   const RAdamScalars S = radam_scalars(step_ptr ? 1 : step, lr, beta1, beta2, eps);
   if (total == 0) return AW_OK;
   int64_t g = (total / 4 + 255) / 256;
   if (g > 4096) g = 4096;
   if (g < 1) g = 1;
-  hipLaunchKernelGGL(radam_ops_kernel, dim3((int)g), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), param,
-                     grad, exp_avg, exp_avg_sq, seg_off, seg_len, seg_wd, seg_active, nseg, total, S, gscale, step_ptr,
-                     ops, zero_grad);
-  return aw::check_launch("aw_radam_step_ops");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (ops)   // the update also writes the operand copies of the updated weights
+    hipLaunchKernelGGL(radam_ops_kernel, dim3((int)g), dim3(256), 0, s, param, grad, exp_avg, exp_avg_sq, seg_off,
+                       seg_len, seg_wd, seg_active, nseg, total, S, gscale, step_ptr, ops, zero_grad);
+  else
+    hipLaunchKernelGGL(radam_kernel, dim3((int)g), dim3(256), 0, s, param, grad, exp_avg, exp_avg_sq, seg_off, seg_len,
+                       seg_wd, seg_active, nseg, total, S, gscale, step_ptr, zero_grad);
+  return aw::check_launch("aw_radam_step");
 }
 
-extern "C" int aw_counter_add(int64_t* counter, int64_t v, void* stream) {
+extern "C" int aw_counter_add(int64_t* counter, int64_t v, int64_t* snapshot, double* zero, int64_t nzero,
+                              void* stream) {
   AW_REQUIRE(counter, "aw_counter_add: null counter");
-  hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(1), 0, reinterpret_cast<hipStream_t>(stream), counter, v,
-                     nullptr);
-  return aw::check_launch("aw_counter_add");
-}
-
-extern "C" int aw_counter_add_snapshot(int64_t* counter, int64_t v, int64_t* snapshot, void* stream) {
-  AW_REQUIRE(counter && snapshot, "aw_counter_add_snapshot: null pointer");
-  hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(1), 0, reinterpret_cast<hipStream_t>(stream), counter, v,
-                     snapshot);
-  return aw::check_launch("aw_counter_add_snapshot");
-}
-
-extern "C" int aw_counter_add_snapshot_zero(int64_t* counter, int64_t v, int64_t* snapshot, double* zero,
-                                            int64_t nzero, void* stream) {
-  AW_REQUIRE(counter && snapshot && nzero >= 0 && (zero || nzero == 0), "aw_counter_add_snapshot_zero: bad args");
+  // counter_add_zero_kernel writes *snapshot: a block to zero needs one
+  AW_REQUIRE(nzero >= 0 && (zero ? snapshot != nullptr : nzero == 0), "aw_counter_add: bad args");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (!zero) {
+    hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(1), 0, s, counter, v, snapshot);
+    return aw::check_launch("aw_counter_add");
+  }
   int64_t g = (nzero + 255) / 256;
   if (g > 1024) g = 1024;
   if (g < 1) g = 1;
-  hipLaunchKernelGGL(counter_add_zero_kernel, dim3((int)g), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     counter, v, snapshot, zero, nzero);
-  return aw::check_launch("aw_counter_add_snapshot_zero");
+  hipLaunchKernelGGL(counter_add_zero_kernel, dim3((int)g), dim3(256), 0, s, counter, v, snapshot, zero, nzero);
+  return aw::check_launch("aw_counter_add");
 }
 
 extern "C" int aw_grad_norm_clip(const float* grad, const int64_t* seg_off, const int64_t* seg_len,

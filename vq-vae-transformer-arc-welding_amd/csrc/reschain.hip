@@ -991,7 +991,7 @@ __global__ __launch_bounds__(256) void res_pack_kernel(PackJobs J) {
   __shared__ __attribute__((aligned(16))) char t[SZ];
   const int x = blockIdx.x, job = blockIdx.y, tid = threadIdx.x;
   const char* __restrict__ W = reinterpret_cast<const char*>(J.src[job]);
-  const bool one_tap = TAPS > 1 && ((J.one_tap >> job) & 1u);   // forward copy only (aw_res_pack_weights_mixed)
+  const bool one_tap = TAPS > 1 && ((J.one_tap >> job) & 1u);   // forward copy only (aw_res_pack_weights, job_taps)
   if (blockIdx.z == 0) {
     uint4* __restrict__ out = reinterpret_cast<uint4*>(J.fwd[job]);
     if (!out) return;
@@ -1156,13 +1156,8 @@ extern "C" int aw_res_chain_bwd(const aw_res_chain_bwd_args* a, void* stream) {
   return aw::check_launch("aw_res_chain_bwd");
 }
 
-extern "C" int aw_res_pack_weights(const void* const* src, void* const* fwd, void* const* bwd, int n, int taps,
-                                   void* stream) {
-  return aw_res_pack_weights_mixed(src, fwd, bwd, nullptr, n, taps, stream);
-}
-
-extern "C" int aw_res_pack_weights_mixed(const void* const* src, void* const* fwd, void* const* bwd,
-                                         const int* job_taps, int n, int taps, void* stream) {
+extern "C" int aw_res_pack_weights(const void* const* src, void* const* fwd, void* const* bwd, const int* job_taps,
+                                   int n, int taps, void* stream) {
   AW_REQUIRE(src && fwd && bwd && n >= 0 && n <= AW_RES_PACK_MAX && (taps == 1 || taps == 3),
              "aw_res_pack_weights: bad args (n must be 0..%d, taps 1 or 3)", AW_RES_PACK_MAX);
   if (n == 0) return AW_OK;

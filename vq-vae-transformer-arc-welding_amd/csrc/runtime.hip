@@ -24,4 +24,4 @@ int check_launch(const char* what) {
 }  // namespace aw
 
 extern "C" const char* aw_last_error(void) { return aw::g_err; }
-extern "C" int aw_version(void) { return 1; }
+extern "C" int aw_version(void) { return AW_ABI_VERSION; }

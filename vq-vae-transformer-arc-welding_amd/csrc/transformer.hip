@@ -1259,9 +1259,8 @@ extern "C" int aw_attn_decode(const void* qkv_new, int64_t B, int n_new, int pos
   return aw::check_launch("aw_attn_decode");
 }
 
-extern "C" int aw_attn_fwd_dropout(const void* qkv, int64_t B, int T, int n_head, int d, int dtype, void* y,
-                                   float* lse, float drop_p, uint64_t drop_seed, const uint64_t* seed_ptr,
-                                   void* stream) {
+extern "C" int aw_attn_fwd(const void* qkv, int64_t B, int T, int n_head, int d, int dtype, void* y, float* lse,
+                           float drop_p, uint64_t drop_seed, const uint64_t* seed_ptr, void* stream) {
   AW_REQUIRE(qkv && y && lse && B >= 0 && T > 0 && n_head > 0 && d % n_head == 0, "aw_attn_fwd: bad args");
   AW_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "aw_attn_fwd: dropout probability must be in [0, 1)");
   const int hs = d / n_head;
@@ -1299,14 +1298,9 @@ extern "C" int aw_attn_fwd_dropout(const void* qkv, int64_t B, int T, int n_head
   return aw::check_launch("aw_attn_fwd");
 }
 
-extern "C" int aw_attn_fwd(const void* qkv, int64_t B, int T, int n_head, int d, int dtype, void* y, float* lse,
-                           void* stream) {
-  return aw_attn_fwd_dropout(qkv, B, T, n_head, d, dtype, y, lse, 0.f, 0ull, nullptr, stream);
-}
-
-extern "C" int aw_attn_bwd_dropout(const void* qkv, const void* y, const void* dy, const float* lse, int64_t B, int T,
-                                   int n_head, int d, int dtype, void* dqkv, float* ws, float drop_p,
-                                   uint64_t drop_seed, const uint64_t* seed_ptr, void* stream) {
+extern "C" int aw_attn_bwd(const void* qkv, const void* y, const void* dy, const float* lse, int64_t B, int T,
+                           int n_head, int d, int dtype, void* dqkv, float* ws, float drop_p, uint64_t drop_seed,
+                           const uint64_t* seed_ptr, void* stream) {
   AW_REQUIRE(qkv && y && dy && lse && dqkv && ws && B >= 0 && T > 0 && n_head > 0 && d % n_head == 0,
              "aw_attn_bwd: bad args");
   AW_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "aw_attn_bwd: dropout probability must be in [0, 1)");
@@ -1355,11 +1349,6 @@ extern "C" int aw_attn_bwd_dropout(const void* qkv, const void* y, const void* d
   }
 #undef AW_B
   return aw::check_launch("aw_attn_bwd");
-}
-
-extern "C" int aw_attn_bwd(const void* qkv, const void* y, const void* dy, const float* lse, int64_t B, int T,
-                           int n_head, int d, int dtype, void* dqkv, float* ws, void* stream) {
-  return aw_attn_bwd_dropout(qkv, y, dy, lse, B, T, n_head, d, dtype, dqkv, ws, 0.f, 0ull, nullptr, stream);
 }
 
 extern "C" int aw_ce_fwd(const float* logits, int64_t R, int V, int64_t ldl, const int64_t* y, int ignore_index,

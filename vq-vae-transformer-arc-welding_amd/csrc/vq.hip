@@ -701,14 +701,14 @@ __global__ void vq_gather_kernel(const float* E, const int64_t* idx, int64_t N, 
 }  // namespace
 
 
-extern "C" int aw_vq_forward_ex2(const float* z, const float* E, int64_t N, int K, int D, float* zq, int64_t* idx,
-                                 float* counts, int count_groups, double* sqerr, void* zq_copy, int copy_dtype,
-                                 void* stream) {
+extern "C" int aw_vq_forward(const float* z, const float* E, int64_t N, int K, int D, float* zq, int64_t* idx,
+                             float* counts, int count_groups, double* sqerr, void* zq_copy, int copy_dtype,
+                             void* stream) {
   AW_REQUIRE(z && E && zq && idx && counts && sqerr, "aw_vq_forward: null pointer");
-  AW_REQUIRE(count_groups >= 1 && count_groups <= AW_VQ_COUNT_GROUPS_MAX, "aw_vq_forward_ex2: count_groups 1..%d",
+  AW_REQUIRE(count_groups >= 1 && count_groups <= AW_VQ_COUNT_GROUPS_MAX, "aw_vq_forward: count_groups 1..%d",
              AW_VQ_COUNT_GROUPS_MAX);
   AW_REQUIRE(!zq_copy || ((copy_dtype == AW_BF16 || copy_dtype == AW_F32) && ((uintptr_t)zq_copy % 16) == 0),
-             "aw_vq_forward_ex: zq_copy must be 16-B aligned bf16 or f32");
+             "aw_vq_forward: zq_copy must be 16-B aligned bf16 or f32");
   const int cbf = copy_dtype == AW_BF16;
   AW_REQUIRE(N >= 0 && K > 0, "aw_vq_forward: bad N/K");
   AW_REQUIRE(((uintptr_t)z % 16) == 0 && ((uintptr_t)E % 16) == 0 && ((uintptr_t)zq % 16) == 0,
@@ -755,47 +755,26 @@ extern "C" int aw_vq_forward_ex2(const float* z, const float* E, int64_t N, int 
   return aw::check_launch("aw_vq_forward");
 }
 
-extern "C" int aw_vq_forward_ex(const float* z, const float* E, int64_t N, int K, int D, float* zq, int64_t* idx,
-                                float* counts, double* sqerr, void* zq_copy, int copy_dtype, void* stream) {
-  return aw_vq_forward_ex2(z, E, N, K, D, zq, idx, counts, 1, sqerr, zq_copy, copy_dtype, stream);
-}
-
-extern "C" int aw_vq_forward(const float* z, const float* E, int64_t N, int K, int D, float* zq, int64_t* idx,
-                             float* counts, double* sqerr, void* stream) {
-  return aw_vq_forward_ex2(z, E, N, K, D, zq, idx, counts, 1, sqerr, nullptr, AW_F32, stream);
-}
-
-extern "C" int aw_vq_finalize_ex(const float* counts, int count_groups, const double* sqerr, int64_t N, int K, int D,
-                                 float beta, float* loss, float* perplexity, void* stream) {
+extern "C" int aw_vq_finalize(const float* counts, int count_groups, const double* sqerr, int64_t N, int K, int D,
+                              float beta, float* loss, float* perplexity, void* stream) {
   AW_REQUIRE(counts && sqerr && loss && perplexity && N > 0 && K > 0 && D > 0, "aw_vq_finalize: bad args");
-  AW_REQUIRE(count_groups >= 1 && count_groups <= AW_VQ_COUNT_GROUPS_MAX, "aw_vq_finalize_ex: count_groups 1..%d",
+  AW_REQUIRE(count_groups >= 1 && count_groups <= AW_VQ_COUNT_GROUPS_MAX, "aw_vq_finalize: count_groups 1..%d",
              AW_VQ_COUNT_GROUPS_MAX);
   hipLaunchKernelGGL(vq_finalize_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), counts,
                      count_groups, sqerr, N, K, D, beta, loss, perplexity);
   return aw::check_launch("aw_vq_finalize");
 }
 
-extern "C" int aw_vq_finalize(const float* counts, const double* sqerr, int64_t N, int K, int D, float beta,
-                              float* loss, float* perplexity, void* stream) {
-  return aw_vq_finalize_ex(counts, 1, sqerr, N, K, D, beta, loss, perplexity, stream);
-}
-
-extern "C" int aw_vq_backward_ex(const float* z, const float* E, const int64_t* idx, const float* g_zq,
-                                 const float* g_loss, int64_t N, int K, int D, float beta, float* dz, float* dE,
-                                 void* dz_copy, int copy_dtype, void* stream) {
+extern "C" int aw_vq_backward(const float* z, const float* E, const int64_t* idx, const float* g_zq,
+                              const float* g_loss, int64_t N, int K, int D, float beta, float* dz, float* dE,
+                              void* dz_copy, int copy_dtype, void* stream) {
   AW_REQUIRE(z && E && idx && dz && dE && N >= 0 && K > 0 && D > 0, "aw_vq_backward: bad args");
-  AW_REQUIRE(!dz_copy || copy_dtype == AW_BF16 || copy_dtype == AW_F32, "aw_vq_backward_ex: bad copy dtype");
+  AW_REQUIRE(!dz_copy || copy_dtype == AW_BF16 || copy_dtype == AW_F32, "aw_vq_backward: bad copy dtype");
   if (N == 0) return AW_OK;
   const int64_t n = N * D;
   hipLaunchKernelGGL(vq_bwd_kernel, dim3(aw_cdiv(n, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), z,
                      E, idx, g_zq, g_loss, N, D, beta, dz, dE, dz_copy, copy_dtype == AW_BF16 ? 1 : 0);
   return aw::check_launch("aw_vq_backward");
-}
-
-extern "C" int aw_vq_backward(const float* z, const float* E, const int64_t* idx, const float* g_zq,
-                              const float* g_loss, int64_t N, int K, int D, float beta, float* dz, float* dE,
-                              void* stream) {
-  return aw_vq_backward_ex(z, E, idx, g_zq, g_loss, N, K, D, beta, dz, dE, nullptr, AW_F32, stream);
 }
 
 extern "C" int aw_vq_onehot(const int64_t* idx, int64_t N, int K, float* onehot, void* stream) {

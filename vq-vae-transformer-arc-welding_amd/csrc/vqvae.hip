@@ -1245,8 +1245,8 @@ extern "C" int aw_bn_finalize(const double* colstats, int64_t n, int H, const fl
   return aw::check_launch("aw_bn_finalize");
 }
 
-extern "C" int aw_unpatch_head_fwd_ex(const void* yv, int y_dtype, int64_t R, int H, int Q, const float* stats,
-                                      const float* w2, const float* b2, float* x_hat, void* stream) {
+extern "C" int aw_unpatch_head_fwd(const void* yv, int y_dtype, int64_t R, int H, int Q, const float* stats,
+                                   const float* w2, const float* b2, float* x_hat, void* stream) {
   AW_REQUIRE(yv && stats && w2 && b2 && x_hat && R >= 0 && Q > 0 && H > 0, "aw_unpatch_head_fwd: bad args");
   AW_REQUIRE(H % 4 == 0 && H <= 256 * HEAD_MAXV, "aw_unpatch_head_fwd: H must be a multiple of 4 and <= 1024");
   AW_REQUIRE(R % Q == 0, "aw_unpatch_head_fwd: rows must be whole windows");
@@ -1278,14 +1278,9 @@ extern "C" int aw_unpatch_head_fwd_ex(const void* yv, int y_dtype, int64_t R, in
   return aw::check_launch("aw_unpatch_head_fwd");
 }
 
-extern "C" int aw_unpatch_head_fwd(const float* y, int64_t R, int H, int Q, const float* stats, const float* w2,
-                                   const float* b2, float* x_hat, void* stream) {
-  return aw_unpatch_head_fwd_ex(y, AW_F32, R, H, Q, stats, w2, b2, x_hat, stream);
-}
-
-extern "C" int aw_unpatch_head_bwd1_ex(const void* yv, int y_dtype, int64_t R, int H, int Q, const float* stats,
-                                       const float* w2, const float* g_xhat, double* gsums, float* gw2, float* gb2,
-                                       float* ggamma, float* gbeta, void* stream) {
+extern "C" int aw_unpatch_head_bwd1(const void* yv, int y_dtype, int64_t R, int H, int Q, const float* stats,
+                                    const float* w2, const float* g_xhat, double* gsums, float* gw2, float* gb2,
+                                    float* ggamma, float* gbeta, void* stream) {
   AW_REQUIRE(yv && stats && w2 && g_xhat && gsums && gw2 && gb2, "aw_unpatch_head_bwd1: null pointer");
   AW_REQUIRE(H % 4 == 0 && H <= 256 * HEAD_MAXV && R % Q == 0, "aw_unpatch_head_bwd1: bad shape");
   AW_REQUIRE(y_dtype == AW_F32 || (y_dtype == AW_BF16 && head_cs_ok(H)),
@@ -1322,15 +1317,9 @@ extern "C" int aw_unpatch_head_bwd1_ex(const void* yv, int y_dtype, int64_t R, i
   return aw::check_launch("aw_unpatch_head_bwd1");
 }
 
-extern "C" int aw_unpatch_head_bwd1(const float* y, int64_t R, int H, int Q, const float* stats, const float* w2,
-                                    const float* g_xhat, double* gsums, float* gw2, float* gb2, float* ggamma,
-                                    float* gbeta, void* stream) {
-  return aw_unpatch_head_bwd1_ex(y, AW_F32, R, H, Q, stats, w2, g_xhat, gsums, gw2, gb2, ggamma, gbeta, stream);
-}
-
-extern "C" int aw_unpatch_head_bwd2_ex(const void* yv, int y_dtype, int64_t R, int H, int Q, const float* stats,
-                                       const float* w2, const float* g_xhat, const double* gsums, int training,
-                                       void* g_y, int gy_dtype, float* db_y, void* stream) {
+extern "C" int aw_unpatch_head_bwd2(const void* yv, int y_dtype, int64_t R, int H, int Q, const float* stats,
+                                    const float* w2, const float* g_xhat, const double* gsums, int training,
+                                    void* g_y, int gy_dtype, float* db_y, void* stream) {
   AW_REQUIRE(yv && stats && w2 && g_xhat && gsums && g_y && db_y, "aw_unpatch_head_bwd2: null pointer");
   AW_REQUIRE(H % 4 == 0 && H <= 256 * HEAD_MAXV && R % Q == 0, "aw_unpatch_head_bwd2: bad shape");
   AW_REQUIRE(y_dtype == AW_F32 || (y_dtype == AW_BF16 && head_cs_ok(H)),
@@ -1405,13 +1394,6 @@ extern "C" int aw_unpatch_head_fwd_bwd1(const void* yv, int y_dtype, int64_t R, 
     hipLaunchKernelGGL(head_fwd_bwd1_kernel<float>, grid, dim3(64 * HFW), 0, s, (const float*)yv, R, stats, w2, b2, x,
                        gscale, gmul, x_hat, g_xhat, sqerr, gsums, gw2, gb2, ggamma, gbeta);
   return aw::check_launch("aw_unpatch_head_fwd_bwd1");
-}
-
-extern "C" int aw_unpatch_head_bwd2(const float* y, int64_t R, int H, int Q, const float* stats, const float* w2,
-                                    const float* g_xhat, const double* gsums, int training, void* g_y, int gy_dtype,
-                                    float* db_y, void* stream) {
-  return aw_unpatch_head_bwd2_ex(y, AW_F32, R, H, Q, stats, w2, g_xhat, gsums, training, g_y, gy_dtype, db_y,
-                                 stream);
 }
 
 extern "C" int aw_mse_fwd(const float* a, const float* b, int64_t n, double* sqerr, void* stream) {

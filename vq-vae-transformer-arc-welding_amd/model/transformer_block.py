@@ -27,7 +27,7 @@ class CausalSelfAttention(nn.Module):
         self.register_buffer("bias", torch.tril(torch.ones(seq_len, seq_len)).view(1, 1, seq_len, seq_len))
         self.n_head = n_head
         self.n_embd = d_model
-        # the probability dropout runs inside the flash attention kernels (aw_attn_fwd_dropout): a counter-based
+        # the probability dropout runs inside the flash attention kernels (aw_attn_fwd, drop_p): a counter-based
         # mask per (b, h, i, j) the backward regenerates; p > 0 takes the runtime-size VALU kernels
         self.attn_pdrop = float(attn_pdrop)
 

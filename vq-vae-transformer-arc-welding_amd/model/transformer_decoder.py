@@ -380,8 +380,8 @@ class MyTransformerDecoder(LightningModule):
         if L0 < 1 or n_new < 0 or L0 + n_new > self.seq_len:
             raise ValueError(f"sample_ids: prompt length {L0} + n_new {n_new} must lie in 1..seq_len = {self.seq_len}")
         N = int(num_samples)
-        if not 1 <= N <= K.nat.BEAM_MAX_W:
-            raise ValueError(f"sample_ids: num_samples = {num_samples} outside 1..{K.nat.BEAM_MAX_W}")
+        if not 1 <= N <= K.nat.AW_BEAM_MAX_W:
+            raise ValueError(f"sample_ids: num_samples = {num_samples} outside 1..{K.nat.AW_BEAM_MAX_W}")
         n_valid = self._n_valid(valid_ids, "sample_ids")
         k = 0 if top_k is None else int(top_k)
         if top_k is not None and not 1 <= k <= n_valid:
@@ -460,13 +460,13 @@ class MyTransformerDecoder(LightningModule):
                              f"{self.seq_len}")
         n_valid = self._n_valid(valid_ids, "beam_search_ids")
         W, R = int(num_beams), int(num_return)
-        if not 1 <= W <= K.nat.BEAM_MAX_W:
-            raise ValueError(f"beam_search_ids: num_beams = {num_beams} outside 1..{K.nat.BEAM_MAX_W}")
+        if not 1 <= W <= K.nat.AW_BEAM_MAX_W:
+            raise ValueError(f"beam_search_ids: num_beams = {num_beams} outside 1..{K.nat.AW_BEAM_MAX_W}")
         if not 1 <= R <= W:
             raise ValueError(f"beam_search_ids: num_return = {num_return} outside 1..num_beams = {W}")
-        if W * n_valid > K.nat.SAMPLE_MAX_V:
+        if W * n_valid > K.nat.AW_SAMPLE_MAX_V:
             raise ValueError(f"beam_search_ids: num_beams * allowed ids = {W} * {n_valid} exceeds the "
-                             f"{K.nat.SAMPLE_MAX_V} candidates one workgroup ranks")
+                             f"{K.nat.AW_SAMPLE_MAX_V} candidates one workgroup ranks")
         dev = x.device
         ids = x[:, None, :].expand(B, R, L0)
         if n_new == 0:
