@@ -834,6 +834,47 @@ int aw_knn(const float* q, int64_t nq, int64_t ldq, const float* x, int64_t nx, 
            float* dist, void* stream);
 int aw_knn_describe(int* tile_q, int* tile_x, int* chunk_d, int* max_k);
 
+/* ------------------------------------------------------------------------------------------------ logistic regression
+ * One loss + gradient evaluation of p <= AW_LOGREG_MAX_P independent binary logistic regressions over one feature
+ * matrix (arcweld.retrieve.logreg_fit): problem c is "class cls[c] against the rest" under its own parameters, so a
+ * one-vs-rest fit and a sweep over regularisation strengths share every read of x.  f32 operands on the f32-input
+ * MFMA (exact f32), f64 sums.  The kernels return raw sums: the regulariser and the 1/N scaling are the caller's.
+ * x: (n, d) f32, rows ldx >= d floats apart, any 4-byte aligned base (16-byte loads in the forward when base and stride
+ * are 16-byte aligned); the row padding and the rows past the end are never read.
+ *
+ * aw_logreg_forward.  w (d, p) f32 and b (p) f32, compact.  Always written: z (n, p) f32 compact, z = x w + b (one
+ * fixed order over d, inside one workgroup; the bias is added last).  With labels -- y (n) int32 class ids and
+ * cls (p) int32 -- also:
+ *   r (n, p) f32 = sigma(z) - t, t_ic = (y_i == cls_c); sigma(z) = (z >= 0 ? 1 : e) / (1 + e), e = expf(-|z|);
+ *   loss (p) f64, loss_c = sum_i softplus(z_ic) - t_ic z_ic, softplus(z) = fl(max(z, 0) + log1pf(e)) in f32, the
+ *     difference and the sum in f64;
+ *   gb (p) f64, gb_c = sum_i r_ic.
+ *   A row with y_i < 0 takes no part: r = 0, and it counts in neither loss nor gb (z is still written).  A class
+ *   that no row has gives t = 0 everywhere.  Each workgroup (aw_logreg_describe's tile_n rows) writes one partial
+ *   per problem to ws; a second kernel adds them in a fixed order.  Labels are given when cls is not NULL (y may
+ *   be NULL with n == 0).  y == NULL and cls == NULL: z only (the decision function of queries); r, loss, gb and ws
+ *   are then ignored.
+ * aw_logreg_grad.  g (d, p) f64 compact, g_kc = sum_i x_ik r_ic, r (n, p) f32 compact.  Grid: (tiles of tile_d dims)
+ * x (row splits); a workgroup accumulates its rows in ascending order on the f32 MFMA and writes an f32 partial to
+ * ws; a second kernel adds the splits' partials in f64 in split order.  splits = 0 picks the count that fills the
+ * device.  The same inputs and the same split count give the same bits on every launch (no float atomics); the
+ * bits may differ between split counts.
+ * ws: aw_logreg_workspace(n, d, p, splits) bytes serve both calls (8-byte aligned).  aw_logreg_describe reports the
+ * forward's rows per workgroup and dims per chunk, the gradient's dims per workgroup and AW_LOGREG_MAX_P.
+ * n == 0: AW_OK; loss, gb (with labels) and g are written as zeros.  Neither call allocates or synchronises.
+ * AW_ERR_ARG and no launch (aw_logreg_workspace returns AW_ERR_ARG): n < 0, d outside 1..2^22 - 1, p outside
+ * 1..AW_LOGREG_MAX_P, splits outside 0..AW_LOGREG_MAX_SPLITS, a stride below d or above 2^22 - 1, a NULL w / b / g,
+ * a NULL x / z with n > 0, y without cls, cls without loss / gb or (n > 0) y / r, a workspace that is missing or too small. */
+#define AW_LOGREG_MAX_P 32
+#define AW_LOGREG_MAX_SPLITS 1024
+int64_t aw_logreg_workspace(int64_t n, int d, int p, int splits);
+int aw_logreg_describe(int* tile_n, int* chunk_d, int* tile_d, int* max_p);
+int aw_logreg_forward(const float* x, int64_t n, int64_t ldx, int d, const float* w, const float* b, int p,
+                      const int* y, const int* cls, float* z, float* r, double* loss, double* gb, void* ws,
+                      int64_t ws_bytes, void* stream);
+int aw_logreg_grad(const float* x, int64_t n, int64_t ldx, int d, const float* r, int p, int splits /* 0 = auto */,
+                   void* ws, int64_t ws_bytes, double* g, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

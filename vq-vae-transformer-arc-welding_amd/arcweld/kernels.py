@@ -871,6 +871,101 @@ def knn(q, x, k, q_group=None, x_group=None, splits=None, idx=None, dist=None, s
     return idx, dist
 
 
+def logreg_describe():
+    """aw_logreg_describe: (tile_n, chunk_d, tile_d, max_p) of the logistic-regression kernels: the forward's rows per
+    workgroup and dims per chunk, the gradient's dims per workgroup, the problem limit (the tests aim at the edges)."""
+    v = [ctypes.c_int(0) for _ in range(4)]
+    call("aw_logreg_describe", *[ctypes.byref(c) for c in v])
+    return tuple(int(c.value) for c in v)
+
+
+def _logreg_x(x, who):
+    if x.dim() != 2 or x.dtype != torch.float32 or (x.shape[1] > 1 and x.stride(1) != 1) or not x.is_cuda:
+        raise nat.NativeError(f"{who}: x must be a 2-d float32 device tensor with contiguous rows, got "
+                              f"{x.dtype} {tuple(x.shape)} strides {tuple(x.stride())}")
+    n, D = x.shape
+    return n, D, (max(x.stride(0), D) if n > 1 else D)
+
+
+def logreg_workspace(n, D, P, splits=None, device=None):
+    """A uint8 workspace of aw_logreg_workspace(n, D, P, splits) bytes: it serves logreg_forward and logreg_grad at
+    these sizes, so a fit allocates it once."""
+    lib = nat.load()
+    ws_bytes = lib.aw_logreg_workspace(n, D, P, 0 if splits is None else int(splits))
+    if ws_bytes < 0:
+        raise nat.NativeError(f"aw_logreg_workspace failed ({ws_bytes}): "
+                              f"{lib.aw_last_error().decode(errors='replace')}")
+    return torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=device)
+
+
+def _logreg_ws(n, D, P, sp, ws, dev):
+    return logreg_workspace(n, D, P, sp, dev) if ws is None else ws
+
+
+def _logreg_out(t, nm, shape, dt, dev, who):
+    if t is None:
+        return torch.empty(shape, dtype=dt, device=dev)
+    if t.dtype != dt or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != dev:
+        raise nat.NativeError(f"{who}: {nm} must be a contiguous {dt} tensor of shape {tuple(shape)} on x's device")
+    return t
+
+
+def logreg_forward(x, w, b, y=None, cls=None, z=None, r=None, loss=None, gb=None, ws=None, stream=None):
+    """aw_logreg_forward: z (n, P) = x (n, D) @ w (D, P) + b (P) in f32 for P <= 32 binary problems; with labels y (n)
+    int32 and cls (P) int32 also r = sigmoid(z) - (y == cls) (n, P) f32 and the f64 sums loss (P) = sum softplus(z) -
+    t z and gb (P) = sum r over the rows with y >= 0; see include/arcweld_amd.h.  x: f32 device tensor with contiguous
+    rows (any row stride >= D, any 4-byte aligned base).  Returns z without labels, (z, r, loss, gb) with them.  ws: an
+    optional uint8 workspace of aw_logreg_workspace bytes to reuse across calls."""
+    who = "logreg_forward"
+    n, D, ldx = _logreg_x(x, who)
+    dev = x.device
+    if w.dim() != 2 or w.dtype != torch.float32 or not w.is_contiguous() or w.device != dev or w.shape[0] != D:
+        raise nat.NativeError(f"{who}: w must be a contiguous float32 tensor of shape ({D}, P) on x's device, got "
+                              f"{w.dtype} {tuple(w.shape)}")
+    P = w.shape[1]
+    if b.dtype != torch.float32 or tuple(b.shape) != (P,) or not b.is_contiguous() or b.device != dev:
+        raise nat.NativeError(f"{who}: b must be a contiguous float32 tensor of {P} elements on x's device")
+    if (y is None) != (cls is None):
+        raise nat.NativeError(f"{who}: y and cls go together")
+    for nm, t, m in (("y", y, n), ("cls", cls, P)):
+        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (m,) or not t.is_contiguous()
+                              or t.device != dev):
+            raise nat.NativeError(f"{who}: {nm} must be a contiguous int32 tensor of {m} elements on x's device")
+    z = _logreg_out(z, "z", (n, P), torch.float32, dev, who)
+    if y is not None:
+        r = _logreg_out(r, "r", (n, P), torch.float32, dev, who)
+        loss = _logreg_out(loss, "loss", (P,), torch.float64, dev, who)
+        gb = _logreg_out(gb, "gb", (P,), torch.float64, dev, who)
+        ws = _logreg_ws(n, D, P, 0, ws, dev)
+    _maybe_timed(stream, "logreg_forward", 2.0 * n * D * P, lambda s: call(
+        "aw_logreg_forward", ptr(x) if n else None, n, ldx, D, ptr(w), ptr(b), P, ptr(y), ptr(cls),
+        ptr(z) if n else None, ptr(r) if (n and y is not None) else None, ptr(loss) if y is not None else None,
+        ptr(gb) if y is not None else None, ptr(ws) if y is not None else None,
+        ws.numel() if y is not None else 0, s),
+        info=lambda: (f"logreg_fwd_kernel P={P} D={D}", 4.0 * n * D + 4.0 * D * P + 8.0 * n * P))
+    return z if y is None else (z, r, loss, gb)
+
+
+def logreg_grad(x, r, splits=None, g=None, ws=None, stream=None):
+    """aw_logreg_grad: g (D, P) f64 = x.T @ r summed over the rows, x (n, D) f32 (contiguous rows, any stride >= D),
+    r (n, P) f32 contiguous.  splits None or 0: the library picks the row split count; the same count gives the same
+    bits on every launch."""
+    who = "logreg_grad"
+    n, D, ldx = _logreg_x(x, who)
+    dev = x.device
+    if r.dim() != 2 or r.dtype != torch.float32 or not r.is_contiguous() or r.device != dev or r.shape[0] != n:
+        raise nat.NativeError(f"{who}: r must be a contiguous float32 tensor of shape ({n}, P) on x's device, got "
+                              f"{r.dtype} {tuple(r.shape)}")
+    P = r.shape[1]
+    sp = 0 if splits is None else int(splits)
+    g = _logreg_out(g, "g", (D, P), torch.float64, dev, who)
+    ws = _logreg_ws(n, D, P, sp, ws, dev)
+    _maybe_timed(stream, "logreg_grad", 2.0 * n * D * P, lambda s: call(
+        "aw_logreg_grad", ptr(x) if n else None, n, ldx, D, ptr(r) if n else None, P, sp, ptr(ws), ws.numel(),
+        ptr(g), s), info=lambda: (f"logreg_grad_kernel P={P} D={D}", 4.0 * n * D + 4.0 * n * P + 8.0 * D * P))
+    return g
+
+
 # ------------------------------------------------------------------------------------------ layouts
 def patchify(x, P, out, stream=None):
     B, L, C = x.shape

@@ -11,6 +11,14 @@ and answers "which training welds does this sequence look like".
   latent_knn_probe  train split = database, val / test = queries: accuracy, per-class accuracy, F1 and the neighbours
 
 The search itself is the HIP kernel; the scaler and the vote are torch plumbing around it.  There is no CPU search.
+
+The same tree's default protocol is the linear one (fit_lr: a StandardScaler, then an L2-regularised one-vs-rest
+logistic regression); its loss + gradient evaluation over the feature matrix is the HIP kernel pair of
+csrc/logreg.hip (arcweld.kernels.logreg_forward / logreg_grad), the optimiser a small batched L-BFGS around it:
+
+  logreg_fit           coefficients of one problem per (class, C), all sharing every pass over the features
+  logreg_decision      decision values of the queries; logreg_predict: the class ids
+  latent_linear_probe  fit on train, {acc, acc_good, acc_bad, f1} on val / test per C, the C with the best val F1
 """
 from __future__ import annotations
 
@@ -18,9 +26,11 @@ import torch
 
 from . import _native as nat
 
-__all__ = ["knn_search", "knn_vote", "latent_knn_probe", "standard_scaler", "MAX_K"]
+__all__ = ["knn_search", "knn_vote", "latent_knn_probe", "standard_scaler", "MAX_K", "logreg_fit", "logreg_decision",
+           "logreg_predict", "latent_linear_probe", "stratified_subsample", "MAX_PROBLEMS"]
 
 MAX_K = nat.AW_KNN_MAX_K
+MAX_PROBLEMS = nat.AW_LOGREG_MAX_P
 _ROWS_PER_CHUNK = 8192
 
 
@@ -249,4 +259,309 @@ def latent_knn_probe(splits, n_cycles, k=1, dataset="latent_vq_vae", vqvae=None,
     if loo:
         own = g["train"] if g["train"] is not None else torch.arange(feats[0].shape[0])
         out["train_loo"] = run(0, own, own)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ linear probe
+_LBFGS_HISTORY = 10
+_LS_C1, _LS_C2, _LS_SHRINK, _LS_MAX = 1e-4, 0.9, 0.5, 30
+_LS_FLAT = 1e-6     # relative agreement of two objective values below which their f32 evaluation noise decides
+
+
+def _check_C(C):
+    seq = [C] if isinstance(C, (int, float)) and not isinstance(C, bool) else C
+    try:
+        vals = [v for v in seq]
+    except TypeError:
+        raise ValueError(f"C: expected a positive float or a sequence of them, got {C!r}") from None
+    if not vals or any(isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 < float(v) < float("inf")
+                       for v in vals):
+        raise ValueError(f"C: expected a positive float or a non-empty sequence of them, got {C!r}")
+    return [float(v) for v in vals]
+
+
+def _check_fit_args(standardize, tol, max_iter):
+    if not isinstance(standardize, bool):
+        raise ValueError(f"standardize: expected a bool, got {standardize!r}")
+    if isinstance(tol, bool) or not isinstance(tol, (int, float)) or not 0 < float(tol) < float("inf"):
+        raise ValueError(f"tol: expected a positive float, got {tol!r}")
+    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 1:
+        raise ValueError(f"max_iter: expected a positive int, got {max_iter!r}")
+
+
+def _logreg_minimize(x, y, cls, Cp, tol, max_iter):
+    """Batched L-BFGS over P <= 32 problems that share x (n, D) f32: theta (P, D + 1) f64 [w | b], n_iter, converged
+    and the objective F (logreg_fit's docstring).  Every trial point is rounded to f32 before it is
+    evaluated and kept rounded, so the state is exactly what the kernels saw and what the caller gets back."""
+    from . import kernels
+    n, D = x.shape
+    P, dev = cls.numel(), x.device
+    lam = 1.0 / (Cp * n)
+    ws = kernels.logreg_workspace(n, D, P, device=dev)
+    z = torch.empty((n, P), dtype=torch.float32, device=dev)
+    r = torch.empty_like(z)
+    loss, gb = (torch.empty(P, dtype=torch.float64, device=dev) for _ in range(2))
+    g = torch.empty((D, P), dtype=torch.float64, device=dev)
+
+    def evaluate(theta):
+        w = theta[:, :D]
+        kernels.logreg_forward(x, w.t().float().contiguous(), theta[:, D].float().contiguous(), y, cls, z=z, r=r,
+                               loss=loss, gb=gb, ws=ws)
+        kernels.logreg_grad(x, r, g=g, ws=ws)
+        return (loss / n + 0.5 * lam * (w * w).sum(1),
+                torch.cat([g.t() / n + lam[:, None] * w, (gb / n)[:, None]], 1))
+
+    theta = torch.zeros((P, D + 1), dtype=torch.float64, device=dev)
+    F, G = evaluate(theta)
+    done = G.abs().amax(1) <= tol
+    stalled = torch.zeros_like(done)
+    has_hist = torch.zeros_like(done)
+    n_iter = torch.zeros(P, dtype=torch.int64, device=dev)
+    gamma = torch.ones(P, dtype=torch.float64, device=dev)
+    hist = []                                      # (s, y, rho), oldest first; a problem's invalid pair is all zeros
+    for _ in range(max_iter):
+        active = ~(done | stalled)
+        if not bool(active.any()):
+            break
+        q, al = G.clone(), []
+        for s_, y_, rho_ in reversed(hist):
+            a = rho_ * (s_ * q).sum(1)
+            q -= a[:, None] * y_
+            al.append(a)
+        q *= gamma[:, None]
+        for (s_, y_, rho_), a in zip(hist, reversed(al)):
+            q += (a - rho_ * (y_ * q).sum(1))[:, None] * s_
+        d = -q
+        gd = (G * d).sum(1)
+        uphill = ~(gd < 0)
+        d = torch.where(uphill[:, None], -G, d)
+        gd = torch.where(uphill, -(G * G).sum(1), gd)
+        alpha = torch.where(has_hist & ~uphill, torch.ones_like(gamma), (1.0 / G.abs().sum(1)).clamp(max=1.0))
+        accepted = ~active                          # a finished problem is frozen at its point
+        theta_new, F_new, G_new = theta, F, G
+        for _ in range(_LS_MAX):
+            trial = torch.where(accepted[:, None], theta_new, (theta + alpha[:, None] * d).float().double())
+            Ft, Gt = evaluate(trial)
+            gtd = (Gt * d).sum(1)
+            # sufficient decrease: Armijo's form, or -- where the two values agree to within their f32 evaluation
+            # noise -- Hager and Zhang's derivative form of it together with the curvature condition (a step that
+            # rounds to nothing fails the latter)
+            ok = (Ft <= F + _LS_C1 * alpha * gd) | ((Ft <= F + _LS_FLAT * F.abs()) & (gtd <= (2 * _LS_C1 - 1) * gd)
+                                                    & (gtd >= _LS_C2 * gd))
+            ok &= ~accepted
+            theta_new = torch.where(ok[:, None], trial, theta_new)
+            F_new, G_new = torch.where(ok, Ft, F_new), torch.where(ok[:, None], Gt, G_new)
+            accepted = accepted | ok
+            if bool(accepted.all()):
+                break
+            alpha = torch.where(accepted, alpha, alpha * _LS_SHRINK)
+        moved = active & accepted
+        s_, y_ = theta_new - theta, G_new - G
+        sy, yy = (s_ * y_).sum(1), (y_ * y_).sum(1)
+        valid = moved & (yy > 0) & (sy > 1e-10 * yy)
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+        hist.append((torch.where(valid[:, None], s_, zero), torch.where(valid[:, None], y_, zero),
+                     torch.where(valid, 1.0 / sy.clamp(min=1e-300), zero)))
+        hist = hist[-_LBFGS_HISTORY:]
+        gamma = torch.where(valid, sy / yy.clamp(min=1e-300), gamma)
+        # a failed search drops the problem's history and retries along the gradient; failing there too ends it
+        failed = active & ~accepted
+        stalled = stalled | (failed & ~has_hist)
+        keep = (~failed).double()
+        hist = [(a * keep[:, None], b * keep[:, None], c * keep) for a, b, c in hist]
+        gamma = torch.where(failed, torch.ones_like(gamma), gamma)
+        has_hist = (has_hist & ~failed) | valid
+        n_iter += moved.long()
+        theta, F, G = theta_new, F_new, G_new
+        done = done | (G.abs().amax(1) <= tol)
+    return theta, n_iter, done, F
+
+
+@torch.no_grad()
+def logreg_fit(features, labels, C=1.0, standardize=True, tol=1e-4, max_iter=1000, n_classes=None):
+    """L2-regularised logistic regression of labels on features: the reference's fit_lr (a StandardScaler, then
+    scikit-learn's LogisticRegression, one-vs-rest), fitted on the device (csrc/logreg.hip).
+
+    features (n, ...) are flattened to (n, D); labels (n,) integer class ids.  C: the inverse regularisation strength,
+    one value or a sequence.  Per problem it minimises scikit-learn's objective
+        F(w, b) = (1 / n) sum_i [softplus(z_i) - t_i z_i] + |w|^2 / (2 C n),   z_i = x_i . w + b,
+    with an unpenalised intercept, and stops a problem when max |grad F| <= tol.  Two classes: one problem per C with
+    positive class 1; more: one per (class, C), one-vs-rest.  All problems share every pass over the features, 32 at a
+    time.  The optimiser is a batched L-BFGS (history 10, backtracking line search on sufficient decrease, f64 state
+    on the device, a finished problem frozen); the kernels see the parameters as f32 and return f64 sums.
+    Returns a dict: coef (n_C, n_problems_per_C, D) and intercept (n_C, n_problems_per_C) f64 in the standardised
+    space, mean and scale (D,) f64 (0 and 1 without standardize), C (n_C,) f64, n_iter, converged, objective (n_C,
+    n_problems_per_C), n_classes, standardize.  Argument errors are ValueErrors naming the argument, raised before any
+    device work."""
+    if isinstance(features, torch.Tensor) and features.dim() >= 2 and features.shape[0] < 1:
+        raise ValueError("features: no rows to fit on")
+    x = _as_rows(features, "features")
+    Cs = _check_C(C)
+    _check_fit_args(standardize, tol, max_iter)
+    if n_classes is not None and (isinstance(n_classes, bool) or not isinstance(n_classes, int) or n_classes < 2):
+        raise ValueError(f"n_classes: expected None or an int >= 2, got {n_classes!r}")
+    labels = torch.as_tensor(labels)
+    if labels.dim() != 1 or labels.shape[0] != x.shape[0] or labels.is_floating_point() or labels.dtype == torch.bool:
+        raise ValueError(f"labels: expected ({x.shape[0]},) integer class ids, got {labels.dtype} of shape "
+                         f"{tuple(labels.shape)}")
+    if x.shape[0] < 1:
+        raise ValueError("features: no rows to fit on")
+    lo, hi = int(labels.min()), int(labels.max())
+    if n_classes is None:
+        n_classes = max(2, hi + 1)
+    if lo < 0 or hi >= n_classes:
+        raise ValueError(f"labels: class ids must lie in 0..{n_classes - 1}, got {lo}..{hi}")
+
+    dev = _device_of(x)
+    x = x.to(dev)
+    D = x.shape[1]
+    if standardize:
+        mean, scale = standard_scaler(x)
+        x = _standardize(x, mean, scale)
+    else:
+        mean = torch.zeros(D, dtype=torch.float64, device=dev)
+        scale = torch.ones(D, dtype=torch.float64, device=dev)
+        x = x.float()
+        x = x if x.stride(-1) == 1 else x.contiguous()
+    y = labels.to(dev, torch.int32).contiguous()
+    classes = [1] if n_classes == 2 else list(range(n_classes))
+    K = len(classes)
+    cls = torch.tensor(classes * len(Cs), dtype=torch.int32, device=dev)
+    Cp = torch.tensor([c for c in Cs for _ in classes], dtype=torch.float64, device=dev)
+    parts = [_logreg_minimize(x, y, cls[o:o + MAX_PROBLEMS].contiguous(), Cp[o:o + MAX_PROBLEMS], float(tol), max_iter)
+             for o in range(0, cls.numel(), MAX_PROBLEMS)]
+    theta, n_iter, conv, obj = (torch.cat([p[i] for p in parts]) for i in range(4))
+    shape = (len(Cs), K)
+    return {"coef": theta[:, :D].reshape(*shape, D), "intercept": theta[:, D].reshape(shape), "mean": mean,
+            "scale": scale, "C": torch.tensor(Cs, dtype=torch.float64, device=dev), "n_iter": n_iter.reshape(shape),
+            "converged": conv.reshape(shape), "objective": obj.reshape(shape), "n_classes": n_classes,
+            "standardize": standardize}
+
+
+def _check_fit(fit):
+    if not isinstance(fit, dict) or not {"coef", "intercept", "mean", "scale", "n_classes", "standardize"} <= set(fit):
+        raise ValueError("fit: expected the dict logreg_fit returns")
+    return fit
+
+
+@torch.no_grad()
+def logreg_decision(fit, queries):
+    """z (n_C, n, n_problems_per_C) f32: the decision function of every fitted problem on the queries (scaled with the
+    fit's mean and scale), 32 problems per pass over the queries (aw_logreg_forward without labels)."""
+    fit = _check_fit(fit)
+    q = _as_rows(queries, "queries")
+    coef, icpt = fit["coef"], fit["intercept"]
+    nC, K, D = coef.shape
+    if q.shape[1] != D:
+        raise ValueError(f"queries: {q.shape[1]} features per row, the fit has {D}")
+    from . import kernels
+    dev = coef.device
+    q = q.to(dev)
+    if fit["standardize"]:
+        q = _standardize(q, fit["mean"], fit["scale"])
+    else:
+        q = q.float()
+        q = q if q.stride(-1) == 1 else q.contiguous()
+    w, b = coef.reshape(nC * K, D).t().float(), icpt.reshape(nC * K).float()
+    z = torch.cat([kernels.logreg_forward(q, w[:, o:o + MAX_PROBLEMS].contiguous(), b[o:o + MAX_PROBLEMS].contiguous())
+                   for o in range(0, nC * K, MAX_PROBLEMS)], 1)
+    return z.reshape(q.shape[0], nC, K).permute(1, 0, 2).contiguous()
+
+
+@torch.no_grad()
+def logreg_predict(fit, queries, decision=None):
+    """Class ids (n_C, n) int64: z > 0 for two classes, else the class of the largest decision value (one-vs-rest;
+    ties to the lowest class).  decision: logreg_decision's output, when the caller has it already."""
+    z = logreg_decision(fit, queries) if decision is None else decision
+    if fit["n_classes"] == 2:
+        return (z[..., 0] > 0).long()
+    return z.argmax(-1)
+
+
+def stratified_subsample(labels, max_samples, seed=0):
+    """Sorted row indices (numpy int64) of a stratified subsample of at most max_samples rows, every row when there
+    are no more than that.  Class c keeps floor(max_samples * n_c / n) rows plus one for the largest remainders (ties
+    to the lower class id); which rows: the first of numpy.random.RandomState(seed).permutation(n_c), classes drawn in
+    ascending order."""
+    import numpy as np
+    y = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels)
+    n = len(y)
+    if n <= max_samples:
+        return np.arange(n, dtype=np.int64)
+    classes, counts = np.unique(y, return_counts=True)
+    share = max_samples * counts.astype(np.int64)
+    take, rem = share // n, share % n
+    for i in np.argsort(-rem, kind="stable")[:max_samples - int(take.sum())]:
+        take[i] += 1
+    rng = np.random.RandomState(seed)
+    rows = [np.flatnonzero(y == c)[np.sort(rng.permutation(int(m))[:int(t)])] for c, m, t in zip(classes, counts, take)]
+    return np.sort(np.concatenate(rows)).astype(np.int64)
+
+
+@torch.no_grad()
+def latent_linear_probe(splits, n_cycles, C=(1.0,), dataset="latent_vq_vae", vqvae=None, standardize=True, tol=1e-4,
+                        max_iter=1000, max_samples=100000, window=200, seed=0):
+    """Linear probe of a feature space: the reference's eval_protocol='linear' (fit_lr) on the features of
+    latent_knn_probe.  A logistic regression per C is fitted on the train split (logreg_fit; above max_samples rows on
+    a seeded stratified subsample, as fit_lr does) and scored on val and test.
+
+    Returns {"per_C": [{"C", "val": m, "test": m}], "C_selected": the C with the best val F1 (the selection rule of
+    the GRU path's val/f1_score_mean; ties to the smaller C), "val" / "test": m at that C plus "pred" (n,) int64 and
+    "decision" (n, n_problems_per_C) f32 device tensors, "fit": logreg_fit's dict, "converged", "n_iter" (per C, over
+    its problems)}, m = {acc, acc_good, acc_bad, f1} as latent_knn_probe reports them."""
+    if dataset not in ("asimow", "latent_vq_vae"):
+        raise ValueError(f"dataset: expected 'asimow' or 'latent_vq_vae', got {dataset!r}")
+    if dataset == "latent_vq_vae" and vqvae is None:
+        raise ValueError("vqvae: dataset latent_vq_vae needs the frozen VQ-VAE")
+    if isinstance(n_cycles, bool) or not isinstance(n_cycles, int) or n_cycles < 1:
+        raise ValueError(f"n_cycles: expected a positive int, got {n_cycles!r}")
+    Cs = _check_C(C)
+    _check_fit_args(standardize, tol, max_iter)
+    if isinstance(max_samples, bool) or not isinstance(max_samples, int) or max_samples < 1:
+        raise ValueError(f"max_samples: expected a positive int, got {max_samples!r}")
+    try:
+        splits = [(x, y) for x, y in splits]
+    except (TypeError, ValueError):
+        raise ValueError("splits: expected three (x, labels) pairs: train, val, test") from None
+    if len(splits) != 3:
+        raise ValueError(f"splits: expected three (x, labels) pairs: train, val, test; got {len(splits)}")
+    names = ("train", "val", "test")
+    for nm, (x, y) in zip(names, splits):
+        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != n_cycles * window:
+            raise ValueError(f"splits: {nm} x must be (n, n_cycles * window = {n_cycles * window}, C), got "
+                             f"{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+        if not isinstance(y, torch.Tensor) or y.dim() != 1 or y.shape[0] != x.shape[0] or y.is_floating_point():
+            raise ValueError(f"splits: {nm} labels must be ({x.shape[0]},) integers")
+    if splits[0][0].shape[0] < 1:
+        raise ValueError("splits: the train split is empty")
+
+    dev = _device_of(*(x for x, _ in splits))
+    keep = stratified_subsample(splits[0][1], max_samples, seed)
+    if len(keep) < splits[0][0].shape[0]:
+        rows = torch.as_tensor(keep, device=splits[0][0].device)
+        splits[0] = (splits[0][0][rows], splits[0][1][rows.to(splits[0][1].device)])
+    feats, labels = [], []
+    for x, y in splits:
+        x = x.to(dev).float()
+        if dataset == "latent_vq_vae":
+            from .data import latent_vectors
+            x = latent_vectors(vqvae, x, n_cycles, window)
+        feats.append(x.reshape(x.shape[0], -1))
+        labels.append(y.to(dev).long())
+    n_classes = max(2, max(int(y.max()) + 1 if y.numel() else 0 for y in labels))
+    fit = logreg_fit(feats[0], labels[0], C=Cs, standardize=standardize, tol=tol, max_iter=max_iter,
+                     n_classes=n_classes)
+    dec = {nm: logreg_decision(fit, feats[i]) for i, nm in ((1, "val"), (2, "test"))}
+    pred = {nm: logreg_predict(fit, None, decision=z) for nm, z in dec.items()}
+    per_C = [{"C": c, **{nm: _metrics(pred[nm][ci], labels[i]) for i, nm in ((1, "val"), (2, "test"))}}
+             for ci, c in enumerate(Cs)]
+    best = None
+    for ci in sorted(range(len(Cs)), key=lambda i: Cs[i]):
+        if best is None or per_C[ci]["val"]["f1"] > per_C[best]["val"]["f1"]:
+            best = ci
+    out = {"per_C": per_C, "C_selected": Cs[best], "fit": fit,
+           "converged": [bool(v) for v in fit["converged"].all(1).cpu()],
+           "n_iter": [int(v) for v in fit["n_iter"].amax(1).cpu()]}
+    for nm in ("val", "test"):
+        out[nm] = {**per_C[best][nm], "pred": pred[nm][best], "decision": dec[nm][best]}
     return out

@@ -1,4 +1,4 @@
-"""k-NN probe of a latent space: how well can weld quality be read off the features, without training anything.
+"""k-NN or linear probe of a latent space: how well can weld quality be read off the features, without training anything.
 
 The train split is the database, val and test are the queries (arcweld.retrieve.latent_knn_probe): every query
 sequence takes the label its ``--k`` nearest training sequences vote for, after the StandardScaler of the reference's
@@ -16,6 +16,15 @@ neighbours.
 "weights", "dataset", "standardize", "n_cycles"}.  ``--neighbours-out`` (optional) receives an .npz with
 '<split>_idx' (n, k) int64, '<split>_dist' (n, k) f32 (squared distances; -1 / +inf past the eligible rows) and
 '<split>_pred' (n,) int64 per split.
+
+``--protocol linear`` is the reference's other protocol, fit_lr: the same StandardScaler, then an L2-regularised
+logistic regression fitted on the train split (arcweld.retrieve.latent_linear_probe, csrc/logreg.hip), one per value
+of ``--C``, all in the same passes over the features; ``--tol`` and ``--max-iter`` bound the fit.  ``--out`` then
+receives {"val" / "test": the metrics at the selected C, "per_C": [{"C", "val", "test"}], "C_selected": the C with the
+best val F1 (ties to the smaller C), "protocol", "dataset", "standardize", "n_cycles", "converged", "n_iter" (per C)}.
+``--model-out`` (optional) receives an .npz with 'coef' (n_C, n_problems, D), 'intercept' (n_C, n_problems), 'mean',
+'scale' (D,) and 'C' (n_C,); the coefficients live in the standardised space.  ``--neighbours-out``, ``--loo``, ``--k``
+and ``--weights`` belong to the k-NN protocol.
 """
 import argparse
 import json
@@ -50,6 +59,11 @@ def parser():
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--out', type=str, default="latent_probe.json")
     p.add_argument('--neighbours-out', type=str, default="")
+    p.add_argument('--protocol', choices=["knn", "linear"], default="knn")
+    p.add_argument('--C', type=float, nargs='+', default=[1.0], help="linear: inverse regularisation strength(s)")
+    p.add_argument('--tol', type=float, default=1e-4, help="linear: stop at max |grad F| <= tol")
+    p.add_argument('--max-iter', type=int, default=1000, help="linear: L-BFGS iterations at most")
+    p.add_argument('--model-out', type=str, default="", help="linear: .npz of the fitted coefficients")
     return p
 
 
@@ -62,11 +76,44 @@ def load_groups(path):
                 if k + "_groups" in f.files}
 
 
+def main_linear(hparams):
+    if hparams.neighbours_out or hparams.loo:
+        raise SystemExit("--neighbours-out and --loo belong to --protocol knn: a linear probe has no neighbours "
+                         "(--model-out writes the fitted coefficients)")
+    if any(not 0 < c < float("inf") for c in hparams.C):
+        raise SystemExit("--C must be positive")
+    if not 0 < hparams.tol < float("inf") or hparams.max_iter < 1:
+        raise SystemExit("--tol must be positive and --max-iter at least 1")
+    from arcweld.retrieve import latent_linear_probe
+    from train_transformer_mtasks import load_splits, load_vqvae
+    dev = torch.device("cuda", torch.cuda.current_device())
+    vqvae = load_vqvae(hparams.vqvae_model, dev) if hparams.dataset == "latent_vq_vae" else None
+    res = latent_linear_probe(load_splits(hparams, dev), hparams.n_cycles, C=list(hparams.C), dataset=hparams.dataset,
+                              vqvae=vqvae, standardize=not hparams.no_standardize, tol=hparams.tol,
+                              max_iter=hparams.max_iter)
+    summary = {name: {m: res[name][m] for m in METRICS} for name in ("val", "test")}
+    summary.update(per_C=res["per_C"], C_selected=res["C_selected"], protocol="linear", dataset=hparams.dataset,
+                   standardize=not hparams.no_standardize, n_cycles=hparams.n_cycles, converged=res["converged"],
+                   n_iter=res["n_iter"])
+    with open(hparams.out, "w") as f:
+        json.dump(summary, f, indent=1, sort_keys=True)
+    if hparams.model_out:
+        np.savez(hparams.model_out, **{k: res["fit"][k].cpu().numpy() for k in ("coef", "intercept", "mean", "scale",
+                                                                                "C")})
+    for name in ("val", "test"):
+        log.info(f"{name} (C = {res['C_selected']:g}): " + ", ".join(f"{m} {res[name][m]:.4f}" for m in METRICS))
+    return res
+
+
 def main(hparams):
     if hparams.dataset == "latent_vq_vae":
         require_checkpoint(hparams.vqvae_model, "--vqvae-model")
     if hparams.n_cycles < 1:
         raise SystemExit("--n-cycles must be at least 1")
+    if hparams.protocol == "linear":
+        return main_linear(hparams)
+    if hparams.model_out:
+        raise SystemExit("--model-out belongs to --protocol linear")
     from arcweld.retrieve import MAX_K, latent_knn_probe
     if not 1 <= hparams.k <= MAX_K:
         raise SystemExit(f"--k must lie in 1..{MAX_K}")
