@@ -875,6 +875,64 @@ int aw_logreg_forward(const float* x, int64_t n, int64_t ldx, int d, const float
 int aw_logreg_grad(const float* x, int64_t n, int64_t ldx, int d, const float* r, int p, int splits /* 0 = auto */,
                    void* ws, int64_t ws_bytes, double* g, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ RBF-SVM probe
+ * The two device steps of an RBF support-vector classifier on a frozen feature space (arcweld.retrieve.svm_fit /
+ * svm_decision): the kernel matrix of two row sets, and the C-SVC dual solved by SMO on a precomputed kernel matrix.
+ *
+ * aw_rbf_gram.  a: (na, d) f32, rows lda >= d floats apart; b: (nb, d) f32, rows ldb >= d apart; any 4-byte aligned
+ * base (16-byte loads when base and stride are 16-byte aligned, guarded 4-byte loads otherwise); the row padding and
+ * the rows past the end are never read.  k: (na, nb) f32, rows ldk >= nb floats apart, any 4-byte aligned base; its
+ * row padding is never written.
+ *   - k[i][j] = expf(fl(-gamma * max(dist(i, j), 0))), dist(i, j) = fl(fl(|a_i|^2 + |b_j|^2) - 2 dot(a_i, b_j)): the
+ *     norms are in-order fmaf chains over the dims, the dot products run on the f32-input MFMA (exact f32) in one fixed
+ *     order over d, always inside one workgroup -- dist is bit for bit the distance aw_knn ranks by.
+ *   - the bits of an element depend on neither the launch geometry nor the run, and since the sum of the norms and
+ *     every product commute, the matrix of a set against itself is bit-symmetric: k[i][j] == k[j][i].  Its diagonal is
+ *     what the formula gives: 1, or a hair below where the rounded dist is positive.
+ *   - a distance that overflows to +inf gives 0.  A NaN distance (a NaN or inf feature, or inf - inf when the norms
+ *     and the dot product both overflow) gives NaN: the caller keeps the features finite and their squares in range.
+ *   - a == b with the same stride and row count: only the tiles on or above the diagonal are computed, each writes its
+ *     mirror image as well -- the same bits as the general path, in about half the time.
+ * Grid: (tiles of a) x (tiles of b), one tile per workgroup; aw_rbf_gram_describe reports the tile sizes (rows of a
+ * and rows of b per workgroup, dims per chunk).
+ * AW_ERR_ARG and no launch: na outside 0..2^31 - 1, nb outside 0..65535 * tile_b, d < 1, lda or ldb below d or above
+ * 2^22 - 1, ldk < nb, a gamma that is not finite and positive, a NULL or misaligned a / b / k (with na, nb > 0).
+ * na == 0 or nb == 0: AW_OK, nothing launched.
+ *
+ * aw_svm_smo.  p <= AW_SVM_MAX_P independent problems over one symmetric kernel matrix k (n, n) f32, rows ldk >= n
+ * floats apart, n <= AW_SVM_MAX_N.  Problem c:  minimise  1/2 alpha' Q alpha - e' alpha  subject to
+ * 0 <= alpha_t <= C[c] and sum_t y_ct alpha_t = 0,  Q_st = y_cs y_ct k_st,  y (p, n) int32 in {-1, 0, +1}, compact.
+ * A row with y = 0 takes no part: its alpha is never written (the caller keeps it 0), it is never selected and its
+ * grad entry is left alone -- the mask by which one-vs-one pairs and folds share one matrix.  Only rows of k
+ * and its diagonal are read, which is where aw_rbf_gram's bit-symmetry matters.
+ *   - C: p doubles in HOST memory, read before the call returns.
+ *   - alpha, grad (p, n) f64, compact, in/out: a solve starts from alpha = 0, grad = -1; the kernel resumes from the
+ *     state it is given and runs at most max_iter further iterations per problem, so a launch always ends.
+ *     n_iter (p) int64 is incremented by the iterations run; gap (p) f64 receives m - M of the state that is left
+ *     (-inf when either candidate set is empty).  A problem with gap <= tol on entry runs no iteration and leaves
+ *     alpha, grad and n_iter as they are, bit for bit.
+ *   - one iteration is libsvm's: with v_t = -y_t G_t, I_up = {y = +1, alpha < C} u {y = -1, alpha > 0} and
+ *     I_low = {y = +1, alpha > 0} u {y = -1, alpha < C}:  i = argmax_{I_up} v (value m);  M = min_{I_low} v;  stop when
+ *     m - M <= tol;  j = argmin over t in I_low with v_t < m of -b^2 / a, b = m - v_t, a = k_ii + k_tt - 2 k_it
+ *     (a <= 0 is replaced by 1e-12);  libsvm's update of (alpha_i, alpha_j) with its clipping to the box;
+ *     G_t += Q_ti dalpha_i + Q_tj dalpha_j for every row of the problem.  All of it in f64 without contraction.
+ *   - every tie goes to the lowest row index and every reduction is a total order, so there are no float atomics and
+ *     the bits are the same on every launch; a solve cut into several launches gives the bits of one launch.
+ * One 1024-thread workgroup per problem, nothing shared between workgroups; the gradient and the rows' status live in
+ * registers, the kernel diagonal and the current row i in LDS.  aw_svm_describe reports the threads per workgroup, the
+ * rows per thread at AW_SVM_MAX_N, AW_SVM_MAX_N and AW_SVM_MAX_P; smaller n run shorter arrays with the same bits.
+ * AW_ERR_ARG and no launch: n outside 0..AW_SVM_MAX_N, p outside 1..AW_SVM_MAX_P, ldk < n, a C that is not finite and
+ * positive, a tol that is not positive, max_iter < 0, a NULL C / n_iter / gap, a NULL k / y / alpha / grad with n > 0.
+ * n == 0: AW_OK, gap = -inf.  Neither call allocates or synchronises. */
+#define AW_SVM_MAX_N 20480
+#define AW_SVM_MAX_P 32
+int aw_rbf_gram(const float* a, int64_t na, int64_t lda, const float* b, int64_t nb, int64_t ldb, int d, float gamma,
+                float* k, int64_t ldk, void* stream);
+int aw_rbf_gram_describe(int* tile_a, int* tile_b, int* chunk_d);
+int aw_svm_smo(const float* k, int n, int64_t ldk, const int* y, const double* C, int p, double tol, int max_iter,
+               double* alpha, double* grad, int64_t* n_iter, double* gap, void* stream);
+int aw_svm_describe(int* threads, int* rows_per_thread, int* max_n, int* max_p);
+
 #ifdef __cplusplus
 }
 #endif

@@ -966,6 +966,96 @@ def logreg_grad(x, r, splits=None, g=None, ws=None, stream=None):
     return g
 
 
+def rbf_gram_describe():
+    """aw_rbf_gram_describe: (tile_a, tile_b, chunk_d) of the Gram kernel: rows of a and of b per workgroup, dims per
+    chunk (the tests aim at the tile edges)."""
+    v = [ctypes.c_int(0) for _ in range(3)]
+    call("aw_rbf_gram_describe", *[ctypes.byref(c) for c in v])
+    return tuple(int(c.value) for c in v)
+
+
+def _rows(t, nm, who):
+    if t.dim() != 2 or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1) or not t.is_cuda:
+        raise nat.NativeError(f"{who}: {nm} must be a 2-d float32 device tensor with contiguous rows, got "
+                              f"{t.dtype} {tuple(t.shape)} strides {tuple(t.stride())}")
+    n, D = t.shape
+    return n, D, (max(t.stride(0), D) if n > 1 else D)
+
+
+def rbf_gram(a, b, gamma, k=None, stream=None):
+    """aw_rbf_gram: k (na, nb) f32 = exp(-gamma |a_i - b_j|^2) with the squared distance as aw_knn forms it (f32 norms
+    and dots, the dots on the f32-input MFMA); see include/arcweld_amd.h.  a (na, D), b (nb, D): f32 device tensors
+    with contiguous rows (any row stride >= D, any 4-byte aligned base); gamma: a float, passed as f32.  k: an optional
+    f32 output with contiguous rows (row stride >= nb; its padding is not written).  The matrix of a set against itself
+    is bit-symmetric.  The range of gamma is the library's to refuse."""
+    who = "rbf_gram"
+    na, D, lda = _rows(a, "a", who)
+    nb, Db, ldb = _rows(b, "b", who)
+    if Db != D or D < 1 or b.device != a.device:
+        raise nat.NativeError(f"{who}: a has {D} features, b has {Db}; need the same D >= 1 on one device")
+    if k is None:
+        k = torch.empty((na, nb), dtype=torch.float32, device=a.device)
+    if k.dim() != 2 or k.dtype != torch.float32 or tuple(k.shape) != (na, nb) or (nb > 1 and k.stride(1) != 1) \
+            or k.device != a.device:
+        raise nat.NativeError(f"{who}: k must be a float32 tensor of shape {(na, nb)} with contiguous rows on a's "
+                              f"device, got {k.dtype} {tuple(k.shape)} strides {tuple(k.stride())}")
+    ldk = max(k.stride(0), nb) if na > 1 else nb
+    _maybe_timed(stream, "rbf_gram", 2.0 * na * nb * D, lambda s: call(
+        "aw_rbf_gram", ptr(a) if na else None, na, lda, ptr(b) if nb else None, nb, ldb, D, float(gamma),
+        ptr(k) if na and nb else None, ldk, s),
+        info=lambda: (f"rbf_gram_kernel D={D}", 4.0 * (na + nb) * D + 4.0 * na * nb))
+    return k
+
+
+def svm_describe():
+    """aw_svm_describe: (threads, rows_per_thread, max_n, max_p) of the SMO kernel: the threads of the one workgroup a
+    problem gets, the rows each owns at max_n, the row and problem limits."""
+    v = [ctypes.c_int(0) for _ in range(4)]
+    call("aw_svm_describe", *[ctypes.byref(c) for c in v])
+    return tuple(int(c.value) for c in v)
+
+
+def svm_smo(k, y, C, tol, max_iter, alpha=None, grad=None, n_iter=None, gap=None, stream=None):
+    """aw_svm_smo: at most max_iter further SMO iterations on each of P <= 32 C-SVC duals over one kernel matrix; see
+    include/arcweld_amd.h.  k (n, n): symmetric f32 device tensor with contiguous rows (row stride >= n); y (P, n)
+    int32 in {-1, 0, +1} (0: the row takes no part); C: P positive floats (a number or a sequence; read on the host).
+    alpha, grad (P, n) f64 are the state, updated in place; None starts a solve (alpha = 0, grad = -1).  n_iter (P)
+    int64 is incremented (None: zeros), gap (P) f64 receives m - M.  Returns (alpha, grad, n_iter, gap).  A launch
+    neither allocates nor synchronises; the ranges of C, tol and max_iter are the library's to refuse."""
+    who = "svm_smo"
+    if k.dim() != 2 or k.dtype != torch.float32 or k.shape[0] != k.shape[1] or not k.is_cuda \
+            or (k.shape[1] > 1 and k.stride(1) != 1):
+        raise nat.NativeError(f"{who}: k must be a square 2-d float32 device tensor with contiguous rows, got "
+                              f"{k.dtype} {tuple(k.shape)} strides {tuple(k.stride())}")
+    n, dev = k.shape[0], k.device
+    ldk = max(k.stride(0), n) if n > 1 else n
+    if y.dim() != 2 or y.dtype != torch.int32 or y.shape[1] != n or not y.is_contiguous() or y.device != dev:
+        raise nat.NativeError(f"{who}: y must be a contiguous int32 tensor of shape (P, {n}) on k's device, got "
+                              f"{y.dtype} {tuple(y.shape)}")
+    P = y.shape[0]
+    Cs = [float(C)] * P if isinstance(C, (int, float)) else [float(c) for c in C]
+    if len(Cs) != P:
+        raise nat.NativeError(f"{who}: C has {len(Cs)} values for {P} problems")
+    if alpha is None:
+        alpha = torch.zeros((P, n), dtype=torch.float64, device=dev)
+    if grad is None:
+        grad = torch.full((P, n), -1.0, dtype=torch.float64, device=dev)
+    if n_iter is None:
+        n_iter = torch.zeros(P, dtype=torch.int64, device=dev)
+    if gap is None:
+        gap = torch.empty(P, dtype=torch.float64, device=dev)
+    for nm, t, shape, dt in (("alpha", alpha, (P, n), torch.float64), ("grad", grad, (P, n), torch.float64),
+                             ("n_iter", n_iter, (P,), torch.int64), ("gap", gap, (P,), torch.float64)):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise nat.NativeError(f"{who}: {nm} must be a contiguous {dt} tensor of shape {shape} on k's device")
+    Ca = (ctypes.c_double * max(P, 1))(*Cs)        # a host array: read before the call returns
+    _maybe_timed(stream, "svm_smo", 0.0, lambda s: call(
+        "aw_svm_smo", ptr(k) if n else None, n, ldk, ptr(y) if n else None, ctypes.cast(Ca, ctypes.c_void_p), P,
+        float(tol), int(max_iter), ptr(alpha) if n else None, ptr(grad) if n else None, ptr(n_iter), ptr(gap), s),
+        info=lambda: (f"svm_smo_kernel n={n} P={P}", 0.0))
+    return alpha, grad, n_iter, gap
+
+
 # ------------------------------------------------------------------------------------------ layouts
 def patchify(x, P, out, stream=None):
     B, L, C = x.shape

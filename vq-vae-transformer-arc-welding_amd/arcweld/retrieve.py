@@ -19,6 +19,14 @@ csrc/logreg.hip (arcweld.kernels.logreg_forward / logreg_grad), the optimiser a 
   logreg_fit           coefficients of one problem per (class, C), all sharing every pass over the features
   logreg_decision      decision values of the queries; logreg_predict: the class ids
   latent_linear_probe  fit on train, {acc, acc_good, acc_bad, f1} on val / test per C, the C with the best val F1
+
+The third protocol of that tree is an RBF support-vector classifier (fit_svm: no scaler, SVC(kernel='rbf',
+gamma='scale', C=0.1)); its kernel matrix and its SMO solver are the HIP kernels of csrc/svm.hip
+(arcweld.kernels.rbf_gram / svm_smo), the host side the problem set-up, rho and the vote:
+
+  svm_fit              dual coefficients of one problem per (class pair, C), all on one Gram matrix; rbf_gamma: 'scale'
+  svm_decision         decision values of the queries against the support rows; svm_predict: the class ids
+  latent_svm_probe     the linear probe's report for the SVM, plus gamma and the support-vector counts
 """
 from __future__ import annotations
 
@@ -27,7 +35,8 @@ import torch
 from . import _native as nat
 
 __all__ = ["knn_search", "knn_vote", "latent_knn_probe", "standard_scaler", "MAX_K", "logreg_fit", "logreg_decision",
-           "logreg_predict", "latent_linear_probe", "stratified_subsample", "MAX_PROBLEMS"]
+           "logreg_predict", "latent_linear_probe", "stratified_subsample", "MAX_PROBLEMS", "rbf_gamma", "svm_pairs",
+           "svm_fit", "svm_decision", "svm_predict", "latent_svm_probe", "MAX_SVM_ROWS"]
 
 MAX_K = nat.AW_KNN_MAX_K
 MAX_PROBLEMS = nat.AW_LOGREG_MAX_P
@@ -560,6 +569,293 @@ def latent_linear_probe(splits, n_cycles, C=(1.0,), dataset="latent_vq_vae", vqv
         if best is None or per_C[ci]["val"]["f1"] > per_C[best]["val"]["f1"]:
             best = ci
     out = {"per_C": per_C, "C_selected": Cs[best], "fit": fit,
+           "converged": [bool(v) for v in fit["converged"].all(1).cpu()],
+           "n_iter": [int(v) for v in fit["n_iter"].amax(1).cpu()]}
+    for nm in ("val", "test"):
+        out[nm] = {**per_C[best][nm], "pred": pred[nm][best], "decision": dec[nm][best]}
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ RBF-SVM probe
+MAX_SVM_ROWS = nat.AW_SVM_MAX_N
+_SMO_CHUNK = 1024               # iterations per aw_svm_smo launch; the gaps are read once per launch
+_SVM_MAX_ITER = 20000           # fit_svm's cap (SVC(max_iter=20_000)), per problem
+
+
+def _check_gamma(gamma):
+    if isinstance(gamma, str):
+        if gamma != "scale":
+            raise ValueError(f"gamma: expected 'scale' or a positive float, got {gamma!r}")
+        return gamma
+    if isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not 0 < float(gamma) < float("inf"):
+        raise ValueError(f"gamma: expected 'scale' or a positive float, got {gamma!r}")
+    return float(gamma)
+
+
+@torch.no_grad()
+def rbf_gamma(features):
+    """scikit-learn's gamma='scale' of the features (n, ...): 1 / (D var), var the population variance over all
+    elements, accumulated in f64 over row chunks on the features' device; 1.0 where the variance is 0.  A float."""
+    if isinstance(features, torch.Tensor) and features.dim() >= 2 and features.shape[0] < 1:
+        raise ValueError("features: no rows")
+    x = _as_rows(features, "features")
+    n, D = x.shape
+    total = torch.zeros((), dtype=torch.float64, device=x.device)
+    for o in range(0, n, _ROWS_PER_CHUNK):
+        total += x[o:o + _ROWS_PER_CHUNK].double().sum()
+    mean = total / (n * D)
+    ss = torch.zeros_like(total)
+    for o in range(0, n, _ROWS_PER_CHUNK):
+        ss += ((x[o:o + _ROWS_PER_CHUNK].double() - mean) ** 2).sum()
+    var = float(ss / (n * D))
+    return 1.0 / (D * var) if var > 0 else 1.0
+
+
+def svm_pairs(n_classes):
+    """(positive class, negative class) of every problem: [(1, 0)] for two classes, else one-vs-one, every a < b as
+    (a, b) in libsvm's order."""
+    return [(1, 0)] if n_classes == 2 else [(a, b) for a in range(n_classes) for b in range(a + 1, n_classes)]
+
+
+def _svm_rho(alpha, grad, y, C):
+    """libsvm's calculate_rho per problem (rows of the (P, n) arguments; C (P,)): the mean of y G over the free rows,
+    else the midpoint of the bounds the rows at the box give (a side without a bound takes the other's; neither: 0)."""
+    yf = y.double()
+    yG = yf * grad
+    act = y != 0
+    at_lo, at_up = act & (alpha <= 0), act & (alpha >= C[:, None])
+    free = act & ~at_lo & ~at_up
+    inf = torch.full_like(yG, float("inf"))
+    ub = torch.where((at_up & (y < 0)) | (at_lo & (y > 0)), yG, inf).amin(1)
+    lb = torch.where((at_up & (y > 0)) | (at_lo & (y < 0)), yG, -inf).amax(1)
+    has_ub, has_lb = torch.isfinite(ub), torch.isfinite(lb)
+    zero = torch.zeros_like(ub)
+    mid = torch.where(has_ub & has_lb, (ub + lb) / 2, torch.where(has_ub, ub, torch.where(has_lb, lb, zero)))
+    n_free = free.sum(1)
+    mean_free = torch.where(free, yG, torch.zeros_like(yG)).sum(1) / n_free.clamp(min=1)
+    return torch.where(n_free > 0, mean_free, mid)
+
+
+@torch.no_grad()
+def svm_fit(features, labels, C=0.1, gamma="scale", standardize=False, tol=1e-3, max_iter=_SVM_MAX_ITER,
+            n_classes=None):
+    """RBF support-vector classifier of labels on features: the reference's fit_svm (np.nan_to_num, NO scaler, then
+    scikit-learn's SVC(kernel='rbf', gamma='scale', C=0.1, tol=1e-3, max_iter=20000)), fitted on the device
+    (csrc/svm.hip): one Gram matrix (aw_rbf_gram), then libsvm's SMO on it (aw_svm_smo).
+
+    features (n, ...) are flattened to (n, D), n <= 20480; labels (n,) integer class ids.  C: one value or a sequence;
+    gamma: 'scale' (rbf_gamma of the features as fitted) or a positive float; the kernel uses its f32 value, which is
+    what the fit reports.  standardize: the scaler of the other two probes, off by default as in fit_svm.  One problem
+    per (class pair, C): two classes give the pair (1, 0) -- y = +1 for class 1 --, more classes every a < b
+    (one-vs-one; rows of other classes are masked out of the pair's problem).  All problems share the Gram matrix and
+    run 32 to a launch, in launches of a fixed iteration chunk, until every problem has gap = m - M <= tol or has run
+    max_iter iterations; the gaps are read once per launch.
+    Returns a dict: dual_coef (n_C, n_pairs, n) f64 = alpha y, rho (n_C, n_pairs) f64 (libsvm's rule), support (n_sv,)
+    int64 -- the rows with any alpha > 0 -- and support_vectors (n_sv, D) f32, their features as the kernel saw them,
+    gamma (float), mean and scale (D,) f64 (0 and 1 without standardize), C (n_C,) f64, pairs [(pos, neg)], n_iter,
+    converged, gap, objective = 1/2 sum alpha (G - 1) and n_support, each (n_C, n_pairs), n_classes, standardize.
+    Argument errors are ValueErrors naming the argument, raised before any device work; more than 20480 rows is one of
+    them (subsample: latent_svm_probe's max_samples).
+    Not offered: fit_svm's small-set branch (C = inf) and its 5-fold cross-validation over a one-point grid."""
+    if isinstance(features, torch.Tensor) and features.dim() >= 2 and features.shape[0] < 1:
+        raise ValueError("features: no rows to fit on")
+    x = _as_rows(features, "features")
+    Cs = _check_C(C)
+    gamma = _check_gamma(gamma)
+    _check_fit_args(standardize, tol, max_iter)
+    if n_classes is not None and (isinstance(n_classes, bool) or not isinstance(n_classes, int) or n_classes < 2):
+        raise ValueError(f"n_classes: expected None or an int >= 2, got {n_classes!r}")
+    labels = torch.as_tensor(labels)
+    if labels.dim() != 1 or labels.shape[0] != x.shape[0] or labels.is_floating_point() or labels.dtype == torch.bool:
+        raise ValueError(f"labels: expected ({x.shape[0]},) integer class ids, got {labels.dtype} of shape "
+                         f"{tuple(labels.shape)}")
+    if x.shape[0] > MAX_SVM_ROWS:
+        raise ValueError(f"features: {x.shape[0]} rows, the solver holds at most {MAX_SVM_ROWS}; fit on a subsample "
+                         f"(latent_svm_probe's max_samples, stratified_subsample)")
+    lo, hi = int(labels.min()), int(labels.max())
+    if n_classes is None:
+        n_classes = max(2, hi + 1)
+    if lo < 0 or hi >= n_classes:
+        raise ValueError(f"labels: class ids must lie in 0..{n_classes - 1}, got {lo}..{hi}")
+
+    from . import kernels
+    dev = _device_of(x)
+    x = torch.nan_to_num(x.to(dev))
+    n, D = x.shape
+    if standardize:
+        mean, scale = standard_scaler(x)
+        x = _standardize(x, mean, scale)
+    else:
+        mean = torch.zeros(D, dtype=torch.float64, device=dev)
+        scale = torch.ones(D, dtype=torch.float64, device=dev)
+        x = x.float()
+        x = x if x.stride(-1) == 1 else x.contiguous()
+    g = rbf_gamma(x) if gamma == "scale" else gamma
+    g = float(torch.tensor(g, dtype=torch.float32))            # the value the kernel receives
+    if not 0 < g < float("inf"):
+        raise ValueError(f"gamma: {gamma!r} is not a positive finite f32 value on these features")
+    K = kernels.rbf_gram(x, x, g)
+
+    pairs = svm_pairs(n_classes)
+    lab = labels.to(dev)
+    y_pairs = torch.stack([(lab == a).to(torch.int32) - (lab == b).to(torch.int32) for a, b in pairs])
+    y = y_pairs.repeat(len(Cs), 1).contiguous()                # problem c * n_pairs + p
+    Cp = [c for c in Cs for _ in pairs]
+    P = len(Cp)
+    alpha = torch.zeros((P, n), dtype=torch.float64, device=dev)
+    grad = torch.full((P, n), -1.0, dtype=torch.float64, device=dev)
+    n_iter = torch.zeros(P, dtype=torch.int64, device=dev)
+    gap = torch.empty(P, dtype=torch.float64, device=dev)
+    for o in range(0, P, MAX_PROBLEMS):
+        sl = slice(o, o + MAX_PROBLEMS)
+        ys, a_, g_, it_, gp_ = y[sl].contiguous(), alpha[sl], grad[sl], n_iter[sl], gap[sl]
+        done = 0
+        while True:
+            step = min(_SMO_CHUNK, max_iter - done)
+            kernels.svm_smo(K, ys, Cp[sl], tol, step, alpha=a_, grad=g_, n_iter=it_, gap=gp_)
+            done += step
+            if done >= max_iter or bool((gp_ <= tol).all()):    # the one read of the gaps per launch
+                break
+    Ct = torch.tensor(Cp, dtype=torch.float64, device=dev)
+    act = y != 0
+    shape = (len(Cs), len(pairs))
+    support = torch.nonzero((alpha > 0).any(0)).flatten()
+    return {"dual_coef": (alpha * y.double()).reshape(*shape, n), "rho": _svm_rho(alpha, grad, y, Ct).reshape(shape),
+            "support": support, "support_vectors": x[support].contiguous(), "gamma": g, "mean": mean, "scale": scale,
+            "C": torch.tensor(Cs, dtype=torch.float64, device=dev), "pairs": pairs,
+            "n_iter": n_iter.reshape(shape), "converged": (gap <= tol).reshape(shape), "gap": gap.reshape(shape),
+            "objective": (0.5 * torch.where(act, alpha * (grad - 1.0), torch.zeros_like(alpha)).sum(1)).reshape(shape),
+            "n_support": (alpha > 0).sum(1).reshape(shape), "n_classes": n_classes, "standardize": standardize}
+
+
+def _check_svm_fit(fit):
+    need = {"dual_coef", "rho", "support", "support_vectors", "gamma", "mean", "scale", "pairs", "n_classes",
+            "standardize"}
+    if not isinstance(fit, dict) or not need <= set(fit):
+        raise ValueError("fit: expected the dict svm_fit returns")
+    return fit
+
+
+@torch.no_grad()
+def svm_decision(fit, queries):
+    """Decision values (n_C, n, n_pairs) f64 of every fitted problem on the queries: aw_rbf_gram of query chunks
+    against the support rows only, an f64 matmul with their dual coefficients, minus rho.  The queries go through
+    nan_to_num and the fit's scaler as the training features did."""
+    fit = _check_svm_fit(fit)
+    q = _as_rows(queries, "queries")
+    sv = fit["support_vectors"]
+    if q.shape[1] != sv.shape[1]:
+        raise ValueError(f"queries: {q.shape[1]} features per row, the fit has {sv.shape[1]}")
+    from . import kernels
+    dev = sv.device
+    q = torch.nan_to_num(q.to(dev))
+    if fit["standardize"]:
+        q = _standardize(q, fit["mean"], fit["scale"])
+    else:
+        q = q.float()
+        q = q if q.stride(-1) == 1 else q.contiguous()
+    coef = fit["dual_coef"][:, :, fit["support"]]                               # (n_C, n_pairs, n_sv)
+    nC, nP, nsv = coef.shape
+    out = torch.empty((nC, q.shape[0], nP), dtype=torch.float64, device=dev)
+    w = coef.reshape(nC * nP, nsv).t().contiguous()
+    for o in range(0, q.shape[0], _ROWS_PER_CHUNK):
+        rows = q[o:o + _ROWS_PER_CHUNK]
+        if nsv:
+            z = kernels.rbf_gram(rows, sv, fit["gamma"]).double() @ w           # (rows, n_C * n_pairs)
+        else:
+            z = torch.zeros((rows.shape[0], nC * nP), dtype=torch.float64, device=dev)
+        out[:, o:o + _ROWS_PER_CHUNK] = z.reshape(rows.shape[0], nC, nP).permute(1, 0, 2)
+    return out - fit["rho"][:, None, :]
+
+
+@torch.no_grad()
+def svm_predict(fit, queries, decision=None):
+    """Class ids (n_C, n) int64.  Two classes: class 1 where the decision > 0.  More: the one-vs-one vote -- a pair
+    votes for its positive class where its decision > 0, else for its negative one --, ties to the lowest class id.
+    decision: svm_decision's output, when the caller has it already."""
+    fit = _check_svm_fit(fit)
+    z = svm_decision(fit, queries) if decision is None else decision
+    K = fit["n_classes"]
+    votes = torch.zeros((*z.shape[:2], K), dtype=torch.int64, device=z.device)
+    for p, (a, b) in enumerate(fit["pairs"]):
+        win = torch.where(z[..., p] > 0, a, b)
+        votes.scatter_add_(2, win[..., None], torch.ones_like(win)[..., None])
+    return votes.argmax(-1) if K > 2 else (votes[..., 1] > votes[..., 0]).long()
+
+
+@torch.no_grad()
+def latent_svm_probe(splits, n_cycles, C=(0.1,), gamma="scale", dataset="latent_vq_vae", vqvae=None,
+                     standardize=False, tol=1e-3, max_iter=_SVM_MAX_ITER, max_samples=20000, window=200, seed=42):
+    """RBF-SVM probe of a feature space: the reference's eval_protocol='svm' (fit_svm) on the features of
+    latent_knn_probe.  A support-vector classifier per C is fitted on the train split (svm_fit; above max_samples rows
+    on a seeded stratified subsample, as fit_svm does above 20 000) and scored on val and test.
+
+    Returns {"per_C": [{"C", "val": m, "test": m, "n_support"}], "C_selected": the C with the best val F1 (ties to the
+    smaller C), "val" / "test": m at that C plus "pred" (n,) int64 and "decision" (n, n_pairs) f64 device tensors,
+    "fit": svm_fit's dict, "gamma", "n_support", "converged", "n_iter" (per C, over its problems)}, m = {acc, acc_good,
+    acc_bad, f1} as latent_knn_probe reports them.
+    Not offered, and refused or left out on purpose: fit_svm's small-set branch (a train split of fewer than 50 rows,
+    or fewer than 5 per class, which it fits with C = inf) is a ValueError; its 5-fold cross-validation is skipped, the
+    grid having one point; the subsample is stratified_subsample's, not scikit-learn's rows."""
+    if dataset not in ("asimow", "latent_vq_vae"):
+        raise ValueError(f"dataset: expected 'asimow' or 'latent_vq_vae', got {dataset!r}")
+    if dataset == "latent_vq_vae" and vqvae is None:
+        raise ValueError("vqvae: dataset latent_vq_vae needs the frozen VQ-VAE")
+    if isinstance(n_cycles, bool) or not isinstance(n_cycles, int) or n_cycles < 1:
+        raise ValueError(f"n_cycles: expected a positive int, got {n_cycles!r}")
+    Cs = _check_C(C)
+    gamma = _check_gamma(gamma)
+    _check_fit_args(standardize, tol, max_iter)
+    if isinstance(max_samples, bool) or not isinstance(max_samples, int) or not 1 <= max_samples <= MAX_SVM_ROWS:
+        raise ValueError(f"max_samples: expected an int in 1..{MAX_SVM_ROWS}, got {max_samples!r}")
+    try:
+        splits = [(x, y) for x, y in splits]
+    except (TypeError, ValueError):
+        raise ValueError("splits: expected three (x, labels) pairs: train, val, test") from None
+    if len(splits) != 3:
+        raise ValueError(f"splits: expected three (x, labels) pairs: train, val, test; got {len(splits)}")
+    names = ("train", "val", "test")
+    for nm, (x, y) in zip(names, splits):
+        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != n_cycles * window:
+            raise ValueError(f"splits: {nm} x must be (n, n_cycles * window = {n_cycles * window}, C), got "
+                             f"{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+        if not isinstance(y, torch.Tensor) or y.dim() != 1 or y.shape[0] != x.shape[0] or y.is_floating_point():
+            raise ValueError(f"splits: {nm} labels must be ({x.shape[0]},) integers")
+    n_train = splits[0][0].shape[0]
+    if n_train < 1:
+        raise ValueError("splits: the train split is empty")
+    n_distinct = int(torch.unique(splits[0][1]).numel())
+    if n_train < 50 or n_train // n_distinct < 5:
+        raise ValueError(f"splits: a train split of {n_train} rows in {n_distinct} classes is the small set fit_svm "
+                         f"fits with C = inf (fewer than 50 rows, or fewer than 5 per class): not offered")
+
+    dev = _device_of(*(x for x, _ in splits))
+    keep = stratified_subsample(splits[0][1], max_samples, seed)
+    if len(keep) < n_train:
+        rows = torch.as_tensor(keep, device=splits[0][0].device)
+        splits[0] = (splits[0][0][rows], splits[0][1][rows.to(splits[0][1].device)])
+    feats, labels = [], []
+    for x, y in splits:
+        x = x.to(dev).float()
+        if dataset == "latent_vq_vae":
+            from .data import latent_vectors
+            x = latent_vectors(vqvae, x, n_cycles, window)
+        feats.append(x.reshape(x.shape[0], -1))
+        labels.append(y.to(dev).long())
+    n_classes = max(2, max(int(y.max()) + 1 if y.numel() else 0 for y in labels))
+    fit = svm_fit(feats[0], labels[0], C=Cs, gamma=gamma, standardize=standardize, tol=tol, max_iter=max_iter,
+                  n_classes=n_classes)
+    dec = {nm: svm_decision(fit, feats[i]) for i, nm in ((1, "val"), (2, "test"))}
+    pred = {nm: svm_predict(fit, None, decision=z) for nm, z in dec.items()}
+    n_sv = [int(v) for v in (fit["dual_coef"] != 0).any(1).sum(1).cpu()]
+    per_C = [{"C": c, "n_support": n_sv[ci],
+              **{nm: _metrics(pred[nm][ci], labels[i]) for i, nm in ((1, "val"), (2, "test"))}}
+             for ci, c in enumerate(Cs)]
+    best = None
+    for ci in sorted(range(len(Cs)), key=lambda i: Cs[i]):
+        if best is None or per_C[ci]["val"]["f1"] > per_C[best]["val"]["f1"]:
+            best = ci
+    out = {"per_C": per_C, "C_selected": Cs[best], "fit": fit, "gamma": fit["gamma"], "n_support": n_sv,
            "converged": [bool(v) for v in fit["converged"].all(1).cpu()],
            "n_iter": [int(v) for v in fit["n_iter"].amax(1).cpu()]}
     for nm in ("val", "test"):

@@ -1,4 +1,4 @@
-"""k-NN or linear probe of a latent space: how well can weld quality be read off the features, without training anything.
+"""k-NN, linear or RBF-SVM probe of a latent space: how well can weld quality be read off the features, without training anything.
 
 The train split is the database, val and test are the queries (arcweld.retrieve.latent_knn_probe): every query
 sequence takes the label its ``--k`` nearest training sequences vote for, after the StandardScaler of the reference's
@@ -25,6 +25,16 @@ best val F1 (ties to the smaller C), "protocol", "dataset", "standardize", "n_cy
 ``--model-out`` (optional) receives an .npz with 'coef' (n_C, n_problems, D), 'intercept' (n_C, n_problems), 'mean',
 'scale' (D,) and 'C' (n_C,); the coefficients live in the standardised space.  ``--neighbours-out``, ``--loo``, ``--k``
 and ``--weights`` belong to the k-NN protocol.
+
+``--protocol svm`` is the third, fit_svm: np.nan_to_num, NO scaler (``--standardize`` switches one on), then an RBF
+support-vector classifier per value of ``--C`` (arcweld.retrieve.latent_svm_probe, csrc/svm.hip: one Gram matrix on
+the f32 MFMA, libsvm's SMO on it), ``--gamma`` a float or ``scale`` (1 / (D var), scikit-learn's default).  ``--C``,
+``--tol`` and ``--max-iter`` resolve per protocol when not given: 1.0 / 1e-4 / 1000 for linear, 0.1 / 1e-3 / 20000
+(fit_svm's values) for svm.  ``--out`` then receives the linear protocol's keys plus "gamma" (the f32 value used) and
+"n_support" (per C; also in every per_C entry).  ``--model-out`` receives an .npz with 'support' (n_sv,) row indices
+into the fitted train rows, 'support_vectors' (n_sv, D), 'dual_coef' (n_C, n_pairs, n_sv), 'rho' (n_C, n_pairs),
+'gamma', 'C' (n_C,), 'mean' and 'scale' (D,).  A train split of fewer than 50 rows, or fewer than 5 per class, is
+refused (fit_svm fits those with C = inf).
 """
 import argparse
 import json
@@ -50,7 +60,8 @@ def parser():
     p.add_argument('--n-cycles', type=int, help='Number of cycles', default=5)
     p.add_argument('--k', type=int, help='Neighbours per query', default=1)
     p.add_argument('--weights', choices=["uniform", "distance"], default="uniform")
-    p.add_argument('--no-standardize', action='store_true', help="search the features as they are")
+    p.add_argument('--no-standardize', action='store_true', help="knn, linear: use the features as they are")
+    p.add_argument('--standardize', action='store_true', help="svm: apply the scaler fit_svm does not have")
     p.add_argument('--loo', action='store_true', help="also: the train split against itself, leave-one-out")
     p.add_argument('--data-npz', type=str, default="")
     p.add_argument('--n-train', type=int, default=1024)
@@ -59,12 +70,42 @@ def parser():
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--out', type=str, default="latent_probe.json")
     p.add_argument('--neighbours-out', type=str, default="")
-    p.add_argument('--protocol', choices=["knn", "linear"], default="knn")
-    p.add_argument('--C', type=float, nargs='+', default=[1.0], help="linear: inverse regularisation strength(s)")
-    p.add_argument('--tol', type=float, default=1e-4, help="linear: stop at max |grad F| <= tol")
-    p.add_argument('--max-iter', type=int, default=1000, help="linear: L-BFGS iterations at most")
-    p.add_argument('--model-out', type=str, default="", help="linear: .npz of the fitted coefficients")
+    p.add_argument('--protocol', choices=["knn", "linear", "svm"], default="knn")
+    p.add_argument('--C', type=float, nargs='+', default=None,
+                   help="linear: inverse regularisation strength(s), default 1.0; svm: box constraint(s), default 0.1")
+    p.add_argument('--tol', type=float, default=None,
+                   help="linear: stop at max |grad F| <= tol, default 1e-4; svm: stop at m - M <= tol, default 1e-3")
+    p.add_argument('--max-iter', type=int, default=None,
+                   help="linear: L-BFGS iterations at most, default 1000; svm: SMO iterations per problem at most, "
+                        "default 20000")
+    p.add_argument('--gamma', type=gamma_arg, default="scale", help="svm: RBF width, a positive float or 'scale'")
+    p.add_argument('--model-out', type=str, default="", help="linear, svm: .npz of the fitted model")
     return p
+
+
+PROTOCOL_DEFAULTS = {"linear": dict(C=[1.0], tol=1e-4, max_iter=1000), "svm": dict(C=[0.1], tol=1e-3, max_iter=20000)}
+
+
+def gamma_arg(text):
+    if text == "scale":
+        return text
+    try:
+        return float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected a float or 'scale', got {text!r}") from None
+
+
+def resolve_fit_args(hparams):
+    """--C, --tol and --max-iter where given, else the protocol's defaults; refuses values outside their ranges."""
+    d = PROTOCOL_DEFAULTS[hparams.protocol]
+    C = list(hparams.C) if hparams.C is not None else d["C"]
+    tol = hparams.tol if hparams.tol is not None else d["tol"]
+    max_iter = hparams.max_iter if hparams.max_iter is not None else d["max_iter"]
+    if any(not 0 < c < float("inf") for c in C):
+        raise SystemExit("--C must be positive")
+    if not 0 < tol < float("inf") or max_iter < 1:
+        raise SystemExit("--tol must be positive and --max-iter at least 1")
+    return C, tol, max_iter
 
 
 def load_groups(path):
@@ -80,17 +121,17 @@ def main_linear(hparams):
     if hparams.neighbours_out or hparams.loo:
         raise SystemExit("--neighbours-out and --loo belong to --protocol knn: a linear probe has no neighbours "
                          "(--model-out writes the fitted coefficients)")
-    if any(not 0 < c < float("inf") for c in hparams.C):
-        raise SystemExit("--C must be positive")
-    if not 0 < hparams.tol < float("inf") or hparams.max_iter < 1:
-        raise SystemExit("--tol must be positive and --max-iter at least 1")
+    if hparams.standardize:
+        raise SystemExit("--standardize belongs to --protocol svm: the linear probe scales unless --no-standardize")
+    if hparams.gamma != "scale":
+        raise SystemExit("--gamma belongs to --protocol svm")
+    C, tol, max_iter = resolve_fit_args(hparams)
     from arcweld.retrieve import latent_linear_probe
     from train_transformer_mtasks import load_splits, load_vqvae
     dev = torch.device("cuda", torch.cuda.current_device())
     vqvae = load_vqvae(hparams.vqvae_model, dev) if hparams.dataset == "latent_vq_vae" else None
-    res = latent_linear_probe(load_splits(hparams, dev), hparams.n_cycles, C=list(hparams.C), dataset=hparams.dataset,
-                              vqvae=vqvae, standardize=not hparams.no_standardize, tol=hparams.tol,
-                              max_iter=hparams.max_iter)
+    res = latent_linear_probe(load_splits(hparams, dev), hparams.n_cycles, C=C, dataset=hparams.dataset,
+                              vqvae=vqvae, standardize=not hparams.no_standardize, tol=tol, max_iter=max_iter)
     summary = {name: {m: res[name][m] for m in METRICS} for name in ("val", "test")}
     summary.update(per_C=res["per_C"], C_selected=res["C_selected"], protocol="linear", dataset=hparams.dataset,
                    standardize=not hparams.no_standardize, n_cycles=hparams.n_cycles, converged=res["converged"],
@@ -105,6 +146,45 @@ def main_linear(hparams):
     return res
 
 
+def main_svm(hparams):
+    if hparams.neighbours_out or hparams.loo:
+        raise SystemExit("--neighbours-out and --loo belong to --protocol knn: an SVM probe has no neighbours "
+                         "(--model-out writes the support vectors)")
+    if hparams.no_standardize:
+        raise SystemExit("--no-standardize belongs to the knn and linear protocols: the SVM probe does not scale "
+                         "unless --standardize")
+    if hparams.gamma != "scale" and not 0 < hparams.gamma < float("inf"):
+        raise SystemExit("--gamma must be positive or 'scale'")
+    C, tol, max_iter = resolve_fit_args(hparams)
+    from arcweld.retrieve import latent_svm_probe
+    from train_transformer_mtasks import load_splits, load_vqvae
+    dev = torch.device("cuda", torch.cuda.current_device())
+    vqvae = load_vqvae(hparams.vqvae_model, dev) if hparams.dataset == "latent_vq_vae" else None
+    try:
+        res = latent_svm_probe(load_splits(hparams, dev), hparams.n_cycles, C=C, gamma=hparams.gamma,
+                               dataset=hparams.dataset, vqvae=vqvae, standardize=hparams.standardize, tol=tol,
+                               max_iter=max_iter)
+    except ValueError as e:
+        raise SystemExit(f"--protocol svm: {e}") from None
+    summary = {name: {m: res[name][m] for m in METRICS} for name in ("val", "test")}
+    summary.update(per_C=res["per_C"], C_selected=res["C_selected"], protocol="svm", dataset=hparams.dataset,
+                   standardize=hparams.standardize, n_cycles=hparams.n_cycles, converged=res["converged"],
+                   n_iter=res["n_iter"], gamma=res["gamma"], n_support=res["n_support"])
+    with open(hparams.out, "w") as f:
+        json.dump(summary, f, indent=1, sort_keys=True)
+    if hparams.model_out:
+        fit = res["fit"]
+        np.savez(hparams.model_out, support=fit["support"].cpu().numpy(),
+                 support_vectors=fit["support_vectors"].cpu().numpy(),
+                 dual_coef=fit["dual_coef"][:, :, fit["support"]].cpu().numpy(), rho=fit["rho"].cpu().numpy(),
+                 gamma=np.float64(fit["gamma"]), C=fit["C"].cpu().numpy(), mean=fit["mean"].cpu().numpy(),
+                 scale=fit["scale"].cpu().numpy())
+    for name in ("val", "test"):
+        log.info(f"{name} (C = {res['C_selected']:g}, gamma = {res['gamma']:g}): "
+                 + ", ".join(f"{m} {res[name][m]:.4f}" for m in METRICS))
+    return res
+
+
 def main(hparams):
     if hparams.dataset == "latent_vq_vae":
         require_checkpoint(hparams.vqvae_model, "--vqvae-model")
@@ -112,8 +192,12 @@ def main(hparams):
         raise SystemExit("--n-cycles must be at least 1")
     if hparams.protocol == "linear":
         return main_linear(hparams)
+    if hparams.protocol == "svm":
+        return main_svm(hparams)
     if hparams.model_out:
-        raise SystemExit("--model-out belongs to --protocol linear")
+        raise SystemExit("--model-out belongs to --protocol linear or svm")
+    if hparams.standardize or hparams.gamma != "scale":
+        raise SystemExit("--standardize and --gamma belong to --protocol svm")
     from arcweld.retrieve import MAX_K, latent_knn_probe
     if not 1 <= hparams.k <= MAX_K:
         raise SystemExit(f"--k must lie in 1..{MAX_K}")
