@@ -5,10 +5,11 @@
 // MFMA'), whose 32 columns are the problems.  f32 operands, f64 sums.
 //
 //   logreg_fwd_kernel    grid (row tiles).  A 256-thread workgroup owns LM = 128 rows; wave w the 32 x 32 block
-//                        (rows 32 w ..) x (problems).  X and W stream through LDS in LK = 32-dim chunks exactly as
-//                        knn.hip stages its operands (range-checked buffer loads -> registers -> LDS, the next chunk's
-//                        loads in flight under the current chunk's MFMAs, two stages, one barrier per chunk); W is
-//                        staged transposed ([problem][dim]) so that both operands are read as float4 along the dims.
+//                        (rows 32 w ..) x (problems).  X and W stream through LDS in LK = 32-dim chunks the way
+//                        pair_tile.h stages its operands (its range-checked buffer loads -> registers -> LDS, the next
+//                        chunk's loads in flight under the current chunk's MFMAs, two stages, one barrier per chunk);
+//                        W is staged transposed ([problem][dim]) so that both operands are read as float4 along the
+//                        dims.
 //                        Epilogue: z = acc + b; with labels r = sigma(z) - t, and per lane the f64 sums of the loss and
 //                        of r over its 16 rows (ascending), the two lane halves added, the four waves added in wave
 //                        order: one (loss, gb) partial per workgroup and problem.
@@ -25,6 +26,7 @@
 //
 // Every sum has one fixed order for given inputs and a given split count: no float atomics anywhere.
 #include "common.h"
+#include "pair_tile.h"
 
 #include <math.h>
 
@@ -45,19 +47,14 @@ static_assert(LP == 32, "the problems are the 32 columns of v_mfma_f32_32x32x2_f
 static_assert(LP * (LK / 4) == LTHREADS, "one W quad per thread per chunk");
 static_assert(2 * L_STAGE * 4 <= 80 * 1024, "forward LDS, two workgroups per CU");
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef unsigned int lr_u32x4 __attribute__((ext_vector_type(4)));
+namespace pt = aw::pt;
+using pt::f32x16;
 
-// Raw buffer descriptors as in knn.hip: an offset past the range returns zeros, so a masked element -- a row past the
-// end, a dim past d, a problem past p -- is a load at LR_BAD_OFF.  Neither the row padding nor rows past the end are
-// ever read.  A descriptor spans at most 128 rows of stride < 2^22 floats: < 2^31 bytes.
-constexpr uint32_t LR_BAD_OFF = 0x80000000u;
-
+// Raw buffer descriptors and the masked loads of pair_tile.h: a masked element -- a row past the end, a dim past d, a
+// problem past p -- reads zeros.  Neither the row padding nor rows past the end are ever read.  A descriptor spans at
+// most 128 rows of stride < 2^22 floats: < 2^31 bytes.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t lr_rsrc(const float* base, int64_t floats) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), (short)0, (int)(uint32_t)(floats * 4), 0x00020000);
-}
-__device__ __forceinline__ float lr_ld1(__amdgpu_buffer_rsrc_t r, bool ok, uint32_t off) {
-  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, ok ? off : LR_BAD_OFF, 0, 0));
 }
 
 template <bool XVEC>
@@ -84,21 +81,11 @@ __global__ __launch_bounds__(LTHREADS, 2) void logreg_fwd_kernel(const float* __
   auto fetch_as = [&](int ch, auto xv) {
     const int d0 = ch * LK + (tid & 7) * 4;
 #pragma unroll
-    for (int i = 0; i < L_XF4; ++i) {
-      const int row = (tid >> 3) + 32 * i;
-      const uint32_t off = (uint32_t)row * ldx_b + 4u * (uint32_t)d0;
-      const bool rok = row < rows;
-      if constexpr (decltype(xv)::value) {
-        const lr_u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(x_rsrc, rok && d0 + 4 <= d ? off : LR_BAD_OFF, 0, 0);
-        pre[i] = make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w));
-      } else {
-        pre[i] = make_float4(lr_ld1(x_rsrc, rok && d0 < d, off), lr_ld1(x_rsrc, rok && d0 + 1 < d, off + 4u),
-                             lr_ld1(x_rsrc, rok && d0 + 2 < d, off + 8u), lr_ld1(x_rsrc, rok && d0 + 3 < d, off + 12u));
-      }
-    }
+    for (int i = 0; i < L_XF4; ++i)
+      pre[i] = pt::ld4<decltype(xv)::value>(x_rsrc, (tid >> 3) + 32 * i, rows, ldx_b, d0, d);
     const int col = tid & 31, k0 = ch * LK + 4 * (tid >> 5);
     const bool cok = col < p;
-    auto wl = [&](int j) { return lr_ld1(w_rsrc, cok && k0 + j < d, 4u * ((uint32_t)(k0 + j) * (uint32_t)p + col)); };
+    auto wl = [&](int j) { return pt::ld1(w_rsrc, cok && k0 + j < d, 4u * ((uint32_t)(k0 + j) * (uint32_t)p + col)); };
     pre[L_XF4] = make_float4(wl(0), wl(1), wl(2), wl(3));
   };
   // only the last chunk of a d % 4 != 0 has a quad that straddles d: it alone takes the 4-byte loads
@@ -213,7 +200,6 @@ __global__ __launch_bounds__(LTHREADS, 2) void logreg_grad_kernel(const float* _
   const int64_t i1 = i0 + rows_per_split < n ? i0 + rows_per_split : n;
   const uint32_t ldx_b = (uint32_t)ldx * 4u;
   const bool cok = jr < p;
-  const uint32_t doff = 4u * (uint32_t)dl;
 
   float4 xa[GR / 2];
   float rb[GR / 2];
@@ -226,16 +212,8 @@ __global__ __launch_bounds__(LTHREADS, 2) void logreg_grad_kernel(const float* _
 #pragma unroll
     for (int s = 0; s < GR / 2; ++s) {
       const int row = 2 * s + h;
-      const bool rok = row < rows;
-      const uint32_t off = (uint32_t)row * ldx_b + doff;
-      if constexpr (XVEC) {
-        const lr_u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(x_rsrc, rok && dl + 4 <= d ? off : LR_BAD_OFF, 0, 0);
-        xa[s] = make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w));
-      } else {
-        xa[s] = make_float4(lr_ld1(x_rsrc, rok && dl < d, off), lr_ld1(x_rsrc, rok && dl + 1 < d, off + 4u),
-                            lr_ld1(x_rsrc, rok && dl + 2 < d, off + 8u), lr_ld1(x_rsrc, rok && dl + 3 < d, off + 12u));
-      }
-      rb[s] = lr_ld1(r_rsrc, rok && cok, 4u * ((uint32_t)row * (uint32_t)p + jr));
+      xa[s] = pt::ld4<XVEC>(x_rsrc, row, rows, ldx_b, dl, d);
+      rb[s] = pt::ld1(r_rsrc, row < rows && cok, 4u * ((uint32_t)row * (uint32_t)p + jr));
     }
   };
 

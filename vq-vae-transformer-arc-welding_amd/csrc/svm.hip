@@ -2,17 +2,14 @@
 // the C-SVC dual solver on a precomputed kernel matrix -- the hot path of arcweld.retrieve.svm_fit / svm_decision.
 //
 //   rbf_gram_kernel   grid (tiles of a, tiles of b); a 256-thread workgroup owns one GA x GB = 128 x 128 tile of k.
-//                     The operands are staged exactly as knn_sweep_kernel (knn.hip) stages them: range-checked raw
-//                     buffer loads -> registers -> LDS in GD = 32-dim chunks, the next chunk's loads in flight under
-//                     the current chunk's MFMAs, two LDS stages, one barrier per chunk, two workgroups per CU.  The
-//                     dots run on the f32-input MFMA (v_mfma_f32_32x32x2_f32: bit for bit an fmaf chain) with the
-//                     rows of a as the A operand, the squared norms accumulate beside them as in-order fmaf chains,
-//                     one staged row per thread.  The epilogue forms dist = fma(-2, dot, fl(|a|^2 + |b|^2)) -- the
-//                     value aw_knn ranks by -- and k = expf(fl(-gamma max(dist, 0))) into LDS as [a row][b row] (over
-//                     the idle stages), then stores the tile row by row: a wave writes 64 consecutive floats (or
-//                     16-byte quads when base and stride allow).
-//                     One element is always accumulated over all of d by one wave in one fixed order (the order of
-//                     knn.hip), and every product and the sum of the norms commute: the bits of an element depend on
+//                     The distances come from the all-pairs tile that knn_sweep_kernel uses (pair_tile.h: staging
+//                     through LDS, dots on the f32-input MFMA with the rows of a as the A operand, norms beside them),
+//                     two workgroups per CU.  The epilogue forms dist = fma(-2, dot, fl(|a|^2 + |b|^2)) -- the
+//                     value aw_knn ranks by, from the same code -- and k = expf(fl(-gamma max(dist, 0))) into LDS as
+//                     [a row][b row] (over the idle stages), then stores the tile row by row: a wave writes 64
+//                     consecutive floats (or 16-byte quads when base and stride allow).
+//                     One element is always accumulated over all of d by one wave in one fixed order, and every
+//                     product and the sum of the norms commute (pair_tile.h): the bits of an element depend on
 //                     neither the grid nor the run, and k(x, x) is bit-symmetric.  So when a and b are the same rows
 //                     only the tiles on or above the diagonal are computed, and each writes its mirror image too.
 //   svm_smo_kernel    one 1024-thread workgroup per problem, no synchronisation between workgroups.  Thread r owns
@@ -28,63 +25,23 @@
 //                     thread) only sizes the arrays: the thread that owns a row and every operation on it are the
 //                     same in every instantiation.  128 VGPRs and no scratch at RPT = 20.
 #include "common.h"
+#include "pair_tile.h"
 
 #include <math.h>
-
-#include <type_traits>
 
 #pragma clang fp contract(off)
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------ Gram matrix
-constexpr int GA = 128;             // rows of a per workgroup (the MFMA's A operand)
-constexpr int GB = 128;             // rows of b per workgroup
-constexpr int GD = 32;              // dims per chunk
-constexpr int GLD = GD + 4;         // staged row stride (floats): 16 rows of a ds_read_b128 cover all 64 banks
-constexpr int GTHREADS = 256;
-constexpr int GKT = GB + 8;         // k tile row stride: the two lane halves (4 rows apart) land 32 banks apart
-constexpr int G_STAGE = (GA + GB) * GLD;                // floats per stage: b rows 0..127, then a rows
-constexpr int G_F4 = (GA + GB) * (GD / 4) / GTHREADS;   // float4 per thread per chunk
-static_assert(GA * GKT <= 2 * G_STAGE, "the k tile overlays the two stages");
-static_assert(GA + GB == GTHREADS, "one staged row per thread for the norms");
+namespace pt = aw::pt;
+constexpr int GA = pt::TA;          // rows of a per workgroup (the MFMA's A operand)
+constexpr int GB = pt::TB;          // rows of b per workgroup
+constexpr int GD = pt::TD;          // dims per chunk
+constexpr int GTHREADS = pt::THREADS;
+constexpr int GKT = pt::OT;         // k tile row stride
 static_assert(GA == GB, "the mirrored tile of a set against itself");
-static_assert((2 * G_STAGE + GA + GB) * 4 <= 80 * 1024, "gram LDS, two workgroups per CU");
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-// Operand loads: raw buffer descriptors over one tile of rows (base = its first row, range = up to the last value of
-// its last row); an offset past the range returns zeros, so a masked quad is a load at GRAM_BAD_OFF (knn.hip).
-// Neither rows past the end nor the row padding are ever read.
-constexpr uint32_t GRAM_BAD_OFF = 0x80000000u;   // >= every range (a tile of rows spans < 2^31 bytes: ld < 2^22)
-typedef unsigned int gram_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t gram_rsrc(const float* base, int64_t row0, int64_t nrows, int64_t ld,
-                                                            int D, int tile_rows, int& rows) {
-  const int64_t left = nrows - row0;
-  rows = (int)(left < tile_rows ? left : tile_rows);
-  const uint32_t bytes = rows > 0 ? (uint32_t)(((int64_t)(rows - 1) * ld + D) * 4) : 0u;
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base + row0 * ld), (short)0, (int)bytes, 0x00020000);
-}
-
-// dims d0 .. d0 + 3 of tile row `row` (zeros for row >= rows and dims >= D).  VEC: one 16-B load (aligned base and
-// stride, no quad of this chunk straddles D); !VEC: four 4-byte loads, each masked on its own.
-template <bool VEC>
-__device__ __forceinline__ float4 gram_ld4(__amdgpu_buffer_rsrc_t r, int row, int rows, uint32_t ld_bytes, int d0,
-                                           int D) {
-  const bool rok = row < rows;
-  const uint32_t off = (uint32_t)row * ld_bytes + 4u * (uint32_t)d0;
-  if constexpr (VEC) {
-    const gram_u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(r, rok && d0 + 4 <= D ? off : GRAM_BAD_OFF, 0, 0);
-    return make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w));
-  } else {
-    auto one = [&](int i) {
-      return __uint_as_float(
-          __builtin_amdgcn_raw_buffer_load_b32(r, rok && d0 + i < D ? off + 4u * i : GRAM_BAD_OFF, 0, 0));
-    };
-    return make_float4(one(0), one(1), one(2), one(3));
-  }
-}
+static_assert((2 * pt::STAGE + GA + GB) * 4 <= 80 * 1024, "gram LDS, two workgroups per CU");
 
 template <bool AVEC, bool BVEC>
 __global__ __launch_bounds__(GTHREADS, 2) void rbf_gram_kernel(const float* __restrict__ a, int64_t na, int64_t lda,
@@ -94,109 +51,35 @@ __global__ __launch_bounds__(GTHREADS, 2) void rbf_gram_kernel(const float* __re
   // a set against itself: the tiles below the diagonal are the mirror images, bit for bit, of those above it (the sum
   // of the norms and every product commute), so the workgroup of tile (y, x) writes them and tile (x, y) has no work
   if (self && blockIdx.x > blockIdx.y) return;
-  __shared__ __attribute__((aligned(16))) float stage[2 * G_STAGE];
+  __shared__ __attribute__((aligned(16))) float stage[2 * pt::STAGE];
   __shared__ float nrm_s[GB + GA];             // |b|^2 of the tile's b rows, then |a|^2 of its a rows
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int h = lane >> 5, jr = lane & 31, wb = w & 1, wa = w >> 1;
+  const int tid = threadIdx.x;
   const int64_t a0 = (int64_t)blockIdx.x * GA, b0 = (int64_t)blockIdx.y * GB;
   const int nch = (D + GD - 1) / GD;
 
-  float4 pre[G_F4];
-  // float4 i of thread tid is quad (tid & 7) of staged row (tid >> 3) + 32 i: b rows for i < G_F4 / 2, a rows after
-  int a_rows, b_rows;
-  const __amdgpu_buffer_rsrc_t a_rsrc = gram_rsrc(a, a0, na, lda, D, GA, a_rows);
-  const __amdgpu_buffer_rsrc_t b_rsrc = gram_rsrc(b, b0, nb, ldb, D, GB, b_rows);
-  const uint32_t lda_b = (uint32_t)lda * 4u, ldb_b = (uint32_t)ldb * 4u;
-  auto fetch_as = [&](int ch, auto av, auto bv) {
-    const int d0 = ch * GD + (tid & 7) * 4;
-#pragma unroll
-    for (int i = 0; i < G_F4; ++i) {
-      const int row = (tid >> 3) + 32 * i;
-      if (i < G_F4 / 2)
-        pre[i] = gram_ld4<decltype(bv)::value>(b_rsrc, row, b_rows, ldb_b, d0, D);
-      else
-        pre[i] = gram_ld4<decltype(av)::value>(a_rsrc, row - GB, a_rows, lda_b, d0, D);
-    }
-  };
-  // only the last chunk of a D % 4 != 0 has a quad that straddles D: it alone takes the 4-byte loads
-  auto fetch = [&](int ch) {
-    if ((D & 3) != 0 && ch == nch - 1)
-      fetch_as(ch, std::false_type{}, std::false_type{});
-    else
-      fetch_as(ch, std::integral_constant<bool, AVEC>{}, std::integral_constant<bool, BVEC>{});
-  };
-  fetch(0);
-  f32x16 acc[2][2];   // [a tile mi][b tile ni]
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
-  float nrm = 0.f;    // the squared norm of staged row `tid`, an in-order fmaf chain over D
+  float4 pre[pt::F4];
+  const pt::Operand ao = pt::operand(a, a0, na, lda, D, GA), bo = pt::operand(b, b0, nb, ldb, D, GB);
+  pt::fetch<BVEC, AVEC>(pre, bo, ao, 0, D, tid);
+  pt::f32x16 acc[2][2];   // [a tile mi][b tile ni]
+  pt::zero(acc);
+  float nrm = 0.f;        // the squared norm of staged row `tid`, an in-order fmaf chain over D
   int buf = 0;
   for (int ch = 0; ch < nch; ++ch) {
-    float* sb = stage + buf * G_STAGE;
-#pragma unroll
-    for (int i = 0; i < G_F4; ++i) {
-      const int f = tid + i * GTHREADS;
-      *reinterpret_cast<float4*>(sb + (f >> 3) * GLD + (f & 7) * 4) = pre[i];
-    }
+    float* sb = stage + buf * pt::STAGE;
+    pt::stage_put(sb, pre, tid);
     __syncthreads();
     // the next chunk's loads fly under this chunk's MFMAs (the stage written next was last read before this barrier)
-    if (ch + 1 < nch) fetch(ch + 1);
-#pragma unroll
-    for (int c = 0; c < GD / 4; ++c) {
-      const float4 v = *reinterpret_cast<const float4*>(sb + tid * GLD + 4 * c);
-      nrm = __builtin_fmaf(v.x, v.x, nrm);
-      nrm = __builtin_fmaf(v.y, v.y, nrm);
-      nrm = __builtin_fmaf(v.z, v.z, nrm);
-      nrm = __builtin_fmaf(v.w, v.w, nrm);
-    }
-    const float* sa = sb + (GB + 64 * wa + jr) * GLD + 4 * h;   // A: rows of a
-    const float* sq = sb + (64 * wb + jr) * GLD + 4 * h;        // B: rows of b
-#pragma unroll
-    for (int g = 0; g < GD / 8; ++g) {
-      float4 a4[2], b4[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        a4[t] = *reinterpret_cast<const float4*>(sa + 32 * t * GLD + 8 * g);
-        b4[t] = *reinterpret_cast<const float4*>(sq + 32 * t * GLD + 8 * g);
-      }
-      const float av[2][4] = {{a4[0].x, a4[0].y, a4[0].z, a4[0].w}, {a4[1].x, a4[1].y, a4[1].z, a4[1].w}};
-      const float bv[2][4] = {{b4[0].x, b4[0].y, b4[0].z, b4[0].w}, {b4[1].x, b4[1].y, b4[1].z, b4[1].w}};
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < 2; ++ni)
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mi][s4], bv[ni][s4], acc[mi][ni], 0, 0, 0);
-    }
+    if (ch + 1 < nch) pt::fetch<BVEC, AVEC>(pre, bo, ao, ch + 1, D, tid);
+    pt::dots(sb, tid, acc, nrm);
     buf ^= 1;
   }
 
-  // ---- the tile to LDS: register r of acc[mi][ni] is a row 64 wa + 32 mi + 8 (r >> 2) + 4 h + (r & 3) against b row
-  //      64 wb + 32 ni + jr.  2 dot is exact, so the fma's one rounding is that of fl(fl(|a|^2 + |b|^2) - 2 dot).
-  nrm_s[tid] = nrm;
-  __syncthreads();   // norms visible; every wave is done reading the stages
+  // ---- the tile to LDS as [a row][b row]: k = expf(fl(-gamma max(dist, 0))) of the distance aw_knn ranks by
   float* kt = stage;
   const float ng = -gamma;
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni) {
-    const int bl = 64 * wb + 32 * ni + jr;
-    const float bb = nrm_s[bl];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int al = 64 * wa + 32 * mi + 8 * (r >> 2) + 4 * h + (r & 3);
-        const float s = __fadd_rn(bb, nrm_s[GB + al]);
-        const float dist = __builtin_fmaf(-2.f, acc[mi][ni][r], s);
-        kt[al * GKT + bl] = expf(__fmul_rn(ng, dist < 0.f ? 0.f : dist));   // a NaN distance stays a NaN
-      }
-  }
-  __syncthreads();
+  pt::dist_tile(kt, nrm_s, nrm, tid, acc, [ng](float dist) {
+    return expf(__fmul_rn(ng, dist < 0.f ? 0.f : dist));   // a NaN distance stays a NaN
+  });
 
   // ---- the store: row al of the tile is GB consecutive floats of k's row a0 + al
   if (kvec) {
