@@ -834,6 +834,50 @@ int aw_knn(const float* q, int64_t nq, int64_t ldq, const float* x, int64_t nx, 
            float* dist, void* stream);
 int aw_knn_describe(int* tile_q, int* tile_x, int* chunk_d, int* max_k);
 
+/* ------------------------------------------------------------------------------------------------ DTW k-NN search
+ * Brute-force exact k-nearest-neighbour search under banded dynamic time warping, f32 throughout
+ * (arcweld.retrieve.dtw_search): the strong raw-signal baseline of the latent-space probe.  Neither the (nq x nx)
+ * distance matrix nor any warping matrix is written to memory.
+ * q: (nq, len, c) f32 queries and x: (nx, len, c) f32 database, time-major (the c channels of one sample contiguous),
+ * rows ldq / ldx >= len * c floats apart; any 4-byte aligned base; the row padding and the rows past the end are never
+ * read.  idx (nq, k) int64 and dist (nq, k) f32, compact, nearest first.
+ *   - the band is Sakoe-Chiba with radius r: cell (i, j) -- sample i of the query, sample j of the database row --
+ *     exists iff |i - j| <= r.  r = 0 is the squared Euclidean distance, r = len - 1 is unconstrained.
+ *   - cost(i, j): acc = 0; for ch = 0 .. c - 1 in order: d = q[i][ch] - x[j][ch] (one f32 subtraction),
+ *     acc = fmaf(d, d, acc).
+ *   - D(0, 0) = cost(0, 0); otherwise D(i, j) = cost(i, j) + min(D(i-1, j-1), D(i-1, j), D(i, j-1)), one f32 addition,
+ *     an absent cell counting as +inf.  dtw(q, x) = D(len - 1, len - 1): the squared-cost "dependent" multichannel
+ *     DTW; no square root is taken.
+ *   - min is exact and every cell has ONE fixed expression, so the bits of dtw(q, x) depend on neither the order the
+ *     cells are evaluated in (rows, columns, anti-diagonals), the launch geometry, nor the run; dtw(q, x) and
+ *     dtw(x, q) are the same bits.  A NaN cell never wins a minimum and everything behind it on every path is
+ *     non-finite, so a row holding a NaN or an inf sample has a non-finite distance to everything.
+ *   - candidates are ranked lexicographically by (dtw as computed, j): the lower database index wins a tie.  Only a
+ *     finite distance is ever taken: NaN / inf rows and f32 overflow never appear as neighbours.
+ *   - q_group (nq) / x_group (nx) int32, each optional: row j is skipped for query i when q_group[i] == x_group[j];
+ *     a NULL on either side means no exclusion.  With fewer than k eligible rows the remaining slots hold idx = -1
+ *     and dist = +inf.
+ * Grid: (query tiles) x (database splits), one lane per (query, database row) pair; every split writes its partial
+ * lists to the workspace and aw_knn's merge kernel picks from splits * k candidates per query in the same (d, j)
+ * order, so the result is bit-identical for every split count.  splits = 0 picks the count that fills the device; ws
+ * needs aw_dtw_knn_workspace(nq, nx, len, c, radius, k, splits) bytes (4-byte aligned).  aw_dtw_knn_describe reports
+ * the tile sizes (queries per workgroup, database rows per tile).
+ * AW_DTW_MAX_WINDOW is the largest band width 2 r + 1: a lane keeps one line of the band in LDS and the workgroup a
+ * ring of 512 query samples that is refilled 64 samples at a time, so 2 r + 1 + 63 <= 512 (csrc/dtw.hip; about
+ * 131 KiB of the CU's 160 KiB at the widest band with 8 channels).
+ * AW_ERR_ARG and no launch (aw_dtw_knn_workspace returns AW_ERR_ARG): nq < 0, nx outside 0..2^31 - 1, len outside
+ * 1..AW_DTW_MAX_LEN, c outside 1..AW_DTW_MAX_C, radius outside 0..len - 1, 2 radius + 1 > AW_DTW_MAX_WINDOW, k outside
+ * 1..AW_KNN_MAX_K, splits outside 0..AW_KNN_MAX_SPLITS, a stride below len * c or above 2^22 - 1, a NULL q / idx /
+ * dist, a workspace that is too small.  nq == 0: AW_OK, nothing launched; nx == 0: every slot is (-1, +inf). */
+#define AW_DTW_MAX_LEN 2000
+#define AW_DTW_MAX_WINDOW 449
+#define AW_DTW_MAX_C 8
+int64_t aw_dtw_knn_workspace(int64_t nq, int64_t nx, int len, int c, int radius, int k, int splits);
+int aw_dtw_knn(const float* q, int64_t nq, int64_t ldq, const float* x, int64_t nx, int64_t ldx, int len, int c,
+               int radius, int k, const int* q_group, const int* x_group, int splits /* 0 = auto */, void* ws,
+               int64_t ws_bytes, int64_t* idx, float* dist, void* stream);
+int aw_dtw_knn_describe(int* tile_q, int* tile_x);
+
 /* ------------------------------------------------------------------------------------------------ logistic regression
  * One loss + gradient evaluation of p <= AW_LOGREG_MAX_P independent binary logistic regressions over one feature
  * matrix (arcweld.retrieve.logreg_fit): problem c is "class cls[c] against the rest" under its own parameters, so a

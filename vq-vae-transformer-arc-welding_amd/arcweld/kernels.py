@@ -871,6 +871,63 @@ def knn(q, x, k, q_group=None, x_group=None, splits=None, idx=None, dist=None, s
     return idx, dist
 
 
+def dtw_knn_describe():
+    """aw_dtw_knn_describe: (tile_q, tile_x) of the DTW search: queries per workgroup and database rows per tile (the
+    tests aim at the tile edges)."""
+    v = [ctypes.c_int(0) for _ in range(2)]
+    call("aw_dtw_knn_describe", *[ctypes.byref(c) for c in v])
+    return tuple(int(c.value) for c in v)
+
+
+def dtw_knn(q, x, length, channels, radius, k, q_group=None, x_group=None, splits=None, idx=None, dist=None,
+            stream=None):
+    """aw_dtw_knn: the k nearest rows of x for every row of q under dynamic time warping inside a Sakoe-Chiba band of
+    `radius` samples (squared sample costs, no square root), f32, ranked by (distance, index); see
+    include/arcweld_amd.h.  q (nq, length * channels), x (nx, length * channels): f32 device tensors whose rows are
+    time-major sequences -- an (n, length, channels) tensor flattened per row -- with contiguous rows (any row stride
+    >= length * channels, any 4-byte aligned base).  q_group (nq) / x_group (nx): optional int32, equal groups are
+    skipped.  splits None or 0: the library picks the database split count.  Returns (idx (nq, k) int64, dist (nq, k)
+    f32); slots past the eligible rows hold (-1, +inf).  The ranges of length, channels, radius, k and splits are the
+    library's to refuse."""
+    for nm, t in (("q", q), ("x", x)):
+        if t.dim() != 2 or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1) or not t.is_cuda:
+            raise nat.NativeError(f"dtw_knn: {nm} must be a 2-d float32 device tensor with contiguous rows, got "
+                                  f"{t.dtype} {tuple(t.shape)} strides {tuple(t.stride())}")
+    length, channels, radius, k = int(length), int(channels), int(radius), int(k)
+    nq, D = q.shape
+    nx = x.shape[0]
+    if x.shape[1] != D or D < 1 or D != length * channels:
+        raise nat.NativeError(f"dtw_knn: q has {D} values per row, x has {x.shape[1]}; need length * channels = "
+                              f"{length} * {channels} on both")
+    ldq = max(q.stride(0), D) if nq > 1 else D
+    ldx = max(x.stride(0), D) if nx > 1 else D
+    for nm, g, n in (("q_group", q_group, nq), ("x_group", x_group, nx)):
+        if g is not None and (g.dtype != torch.int32 or tuple(g.shape) != (n,) or not g.is_contiguous()
+                              or g.device != q.device):
+            raise nat.NativeError(f"dtw_knn: {nm} must be a contiguous int32 tensor of {n} elements on q's device")
+    sp = 0 if splits is None else int(splits)
+    if idx is None:
+        idx = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=q.device)
+    if dist is None:
+        dist = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=q.device)
+    for nm, t, dt in (("idx", idx, torch.int64), ("dist", dist, torch.float32)):
+        if t.dtype != dt or tuple(t.shape) != (nq, k) or not t.is_contiguous() or t.device != q.device:
+            raise nat.NativeError(f"dtw_knn: {nm} must be a contiguous {dt} tensor of shape {(nq, k)} on q's device")
+    lib = nat.load()
+    ws_bytes = lib.aw_dtw_knn_workspace(nq, nx, length, channels, radius, k, sp)
+    if ws_bytes < 0:
+        raise nat.NativeError(f"aw_dtw_knn_workspace failed ({ws_bytes}): "
+                              f"{lib.aw_last_error().decode(errors='replace')}")
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=q.device)
+    cells = float(length * (2 * radius + 1) - radius * (radius + 1))      # cells of the band, 0 <= radius < length
+    _maybe_timed(stream, "dtw_knn", float(nq) * nx * cells, lambda s: call(
+        "aw_dtw_knn", ptr(q), nq, ldq, ptr(x) if nx else None, nx, ldx, length, channels, radius, k, ptr(q_group),
+        ptr(x_group), sp, ptr(ws), ws.numel(), ptr(idx), ptr(dist), s),
+        info=lambda: (f"dtw_sweep_kernel k={k} L={length} C={channels} r={radius}",
+                      4.0 * (nq + nx) * D + 12.0 * nq * k))
+    return idx, dist
+
+
 def logreg_describe():
     """aw_logreg_describe: (tile_n, chunk_d, tile_d, max_p) of the logistic-regression kernels: the forward's rows per
     workgroup and dims per chunk, the gradient's dims per workgroup, the problem limit (the tests aim at the edges)."""

@@ -10,6 +10,9 @@ and answers "which training welds does this sequence look like".
   knn_vote          class votes of the neighbours' labels -> (pred, votes); plain torch on the inputs' device
   latent_knn_probe  train split = database, val / test = queries: accuracy, per-class accuracy, F1 and the neighbours
 
+  dtw_search        the same under banded dynamic time warping of (n, L, C) sequences (arcweld.kernels.dtw_knn,
+                    csrc/dtw.hip): the strong baseline for raw weld cycles, which differ in phase and duration
+
 The search itself is the HIP kernel; the scaler and the vote are torch plumbing around it.  There is no CPU search.
 
 The same tree's default protocol is the linear one (fit_lr: a StandardScaler, then an L2-regularised one-vs-rest
@@ -36,9 +39,11 @@ from . import _native as nat
 
 __all__ = ["knn_search", "knn_vote", "latent_knn_probe", "standard_scaler", "MAX_K", "logreg_fit", "logreg_decision",
            "logreg_predict", "latent_linear_probe", "stratified_subsample", "MAX_PROBLEMS", "rbf_gamma", "svm_pairs",
-           "svm_fit", "svm_decision", "svm_predict", "latent_svm_probe", "MAX_SVM_ROWS"]
+           "svm_fit", "svm_decision", "svm_predict", "latent_svm_probe", "MAX_SVM_ROWS", "dtw_search", "MAX_DTW_LEN",
+           "MAX_DTW_WINDOW", "MAX_DTW_CHANNELS"]
 
 MAX_K = nat.AW_KNN_MAX_K
+MAX_DTW_LEN, MAX_DTW_WINDOW, MAX_DTW_CHANNELS = nat.AW_DTW_MAX_LEN, nat.AW_DTW_MAX_WINDOW, nat.AW_DTW_MAX_C
 MAX_PROBLEMS = nat.AW_LOGREG_MAX_P
 _ROWS_PER_CHUNK = 8192
 
@@ -145,6 +150,77 @@ def knn_search(queries, database, k=1, standardize=True, q_group=None, x_group=N
     return idx, (dist.sqrt() if sqrt else dist)
 
 
+def _check_radius(radius, L):
+    """The band radius in samples: None is L - 1 (unconstrained); limits from the header (MAX_DTW_WINDOW)."""
+    if radius is None:
+        radius = L - 1
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= L - 1:
+        raise ValueError(f"radius: expected None or an int in 0..L - 1 = {L - 1}, got {radius!r}")
+    if 2 * radius + 1 > MAX_DTW_WINDOW:
+        raise ValueError(f"radius: {radius} gives a band of {2 * radius + 1} samples, the search holds at most "
+                         f"{MAX_DTW_WINDOW} (radius <= {(MAX_DTW_WINDOW - 1) // 2})")
+    return radius
+
+
+def _as_sequences(t, name):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name}: expected a torch tensor, got {type(t).__name__}")
+    if t.dim() != 3:
+        raise ValueError(f"{name}: expected (n, L, C) sequences, got shape {tuple(t.shape)}")
+    if not t.is_floating_point():
+        raise ValueError(f"{name}: expected a floating-point tensor, got {t.dtype}")
+    if not 1 <= t.shape[1] <= MAX_DTW_LEN:
+        raise ValueError(f"{name}: sequence length {t.shape[1]} outside 1..{MAX_DTW_LEN}")
+    if not 1 <= t.shape[2] <= MAX_DTW_CHANNELS:
+        raise ValueError(f"{name}: {t.shape[2]} channels outside 1..{MAX_DTW_CHANNELS}")
+    return t
+
+
+@torch.no_grad()
+def dtw_search(queries, database, k=1, radius=None, standardize=False, q_group=None, x_group=None, sqrt=False):
+    """The k nearest database sequences of every query under dynamic time warping (csrc/dtw.hip).
+
+    queries (nq, L, C) and database (nx, L, C) share L <= 2000 and C <= 8.  The distance is the squared-cost
+    "dependent" multichannel DTW inside a Sakoe-Chiba band: sample i of the query may be matched with sample j of the
+    database row iff |i - j| <= radius; radius None means L - 1 (no constraint), radius 0 is the squared Euclidean
+    distance; 2 radius + 1 <= 449.  standardize: a PER-CHANNEL scaler fitted on the database,
+    standard_scaler(database.reshape(-1, C)), applied to both sides (a per-position scaler would erase the axis DTW
+    warps, so it is not offered).  q_group / x_group, the ranking, ties and the (-1, +inf) slots are knn_search's.
+    Returns idx (nq, k) int64 and dist (nq, k) f32 on the device: the DTW cost, or its square root with sqrt=True.
+    Argument errors are ValueErrors naming the argument, raised before any device work."""
+    q, x = _as_sequences(queries, "queries"), _as_sequences(database, "database")
+    if q.shape[1:] != x.shape[1:]:
+        raise ValueError(f"database: sequences of shape {tuple(x.shape[1:])}, queries have {tuple(q.shape[1:])}")
+    L, C = x.shape[1], x.shape[2]
+    k = _check_k(k)
+    radius = _check_radius(radius, L)
+    if x.shape[0] >= 2 ** 31:
+        raise ValueError(f"database: {x.shape[0]} rows, the search indexes at most 2^31 - 1")
+    if not isinstance(standardize, bool):
+        raise ValueError(f"standardize: expected a bool, got {standardize!r}")
+    if not isinstance(sqrt, bool):
+        raise ValueError(f"sqrt: expected a bool, got {sqrt!r}")
+    qg, xg = _as_group(q_group, q.shape[0], "q_group"), _as_group(x_group, x.shape[0], "x_group")
+
+    from . import kernels
+    dev = _device_of(q, x)
+    q, x = q.to(dev).reshape(q.shape[0], L * C), x.to(dev).reshape(x.shape[0], L * C)
+    if standardize:
+        mean, scale = standard_scaler(x.reshape(-1, C))
+        q = _standardize(q.reshape(-1, C), mean, scale).reshape(-1, L * C)
+        x = _standardize(x.reshape(-1, C), mean, scale).reshape(-1, L * C)
+    else:
+        q, x = q.float(), x.float()
+        q = q if q.stride(-1) == 1 else q.contiguous()
+        x = x if x.stride(-1) == 1 else x.contiguous()
+    if qg is not None and xg is not None:
+        qg, xg = qg.to(dev, torch.int32).contiguous(), xg.to(dev, torch.int32).contiguous()
+    else:
+        qg = xg = None
+    idx, dist = kernels.dtw_knn(q, x, L, C, radius, k, q_group=qg, x_group=xg)
+    return idx, (dist.sqrt() if sqrt else dist)
+
+
 @torch.no_grad()
 def knn_vote(idx, dist, labels, n_classes=2, weights="uniform"):
     """Class votes of the neighbours: pred (n,) int64 and votes (n, n_classes) f64, on idx's device.
@@ -198,7 +274,7 @@ def _metrics(pred, target):
 
 @torch.no_grad()
 def latent_knn_probe(splits, n_cycles, k=1, dataset="latent_vq_vae", vqvae=None, weights="uniform", standardize=True,
-                     loo=False, groups=None, window=200):
+                     loo=False, groups=None, window=200, metric="euclidean", radius=None):
     """k-NN probe of a feature space: the train split is the database, val and test are the queries.
 
     splits: [(x (n, n_cycles*window, C), labels (n,))] for train / val / test, as ClassificationDataModule takes them.
@@ -208,9 +284,20 @@ def latent_knn_probe(splits, n_cycles, k=1, dataset="latent_vq_vae", vqvae=None,
     idx, dist (n, k), pred (n,): device tensors}.  loo=True adds "train_loo": the train split against itself, each row
     excluded from its own neighbours -- or, with groups["train"], everything of its own group (leave-one-run-out).
     groups: optional {"train" / "val" / "test": (n,) integer ids}; a val / test split with ids is searched with its
-    rows' own groups excluded from the database as well."""
+    rows' own groups excluded from the database as well.
+    metric "dtw" (dataset "asimow" only: latent rows are (n_cycles, 1024)-shaped vectors, not time series) searches
+    the raw (n, n_cycles * window, C) sequences under dynamic time warping (dtw_search) in a band of `radius` samples
+    (None: unconstrained); standardize is then dtw_search's per-channel scaler, fitted on the train split; dist is
+    the DTW cost.  Voting, metrics, loo and groups are the same.  radius belongs to metric "dtw"."""
     if dataset not in ("asimow", "latent_vq_vae"):
         raise ValueError(f"dataset: expected 'asimow' or 'latent_vq_vae', got {dataset!r}")
+    if metric not in ("euclidean", "dtw"):
+        raise ValueError(f"metric: expected 'euclidean' or 'dtw', got {metric!r}")
+    if metric == "dtw" and dataset != "asimow":
+        raise ValueError("metric: 'dtw' warps the time axis of the raw cycles and needs dataset 'asimow'; the rows of "
+                         "dataset 'latent_vq_vae' are (n_cycles, 1024)-shaped latent vectors, not time series")
+    if metric != "dtw" and radius is not None:
+        raise ValueError(f"radius: belongs to metric 'dtw', got {radius!r} with metric {metric!r}")
     if dataset == "latent_vq_vae" and vqvae is None:
         raise ValueError("vqvae: dataset latent_vq_vae needs the frozen VQ-VAE")
     if isinstance(n_cycles, bool) or not isinstance(n_cycles, int) or n_cycles < 1:
@@ -240,6 +327,12 @@ def latent_knn_probe(splits, n_cycles, k=1, dataset="latent_vq_vae", vqvae=None,
         if key not in names:
             raise ValueError(f"groups: unknown split {key!r} (expected train / val / test)")
     g = {nm: _as_group(groups.get(nm), splits[i][0].shape[0], f"groups[{nm!r}]") for i, nm in enumerate(names)}
+    if metric == "dtw":
+        for nm, (x, _) in zip(names, splits):
+            _as_sequences(x, f"splits: {nm} x")
+            if x.shape[2] != splits[0][0].shape[2]:
+                raise ValueError(f"splits: {nm} x has {x.shape[2]} channels, train has {splits[0][0].shape[2]}")
+        radius = _check_radius(radius, n_cycles * window)
 
     dev = _device_of(*(x for x, _ in splits))
     feats, labels = [], []
@@ -248,15 +341,23 @@ def latent_knn_probe(splits, n_cycles, k=1, dataset="latent_vq_vae", vqvae=None,
         if dataset == "latent_vq_vae":
             from .data import latent_vectors
             x = latent_vectors(vqvae, x, n_cycles, window)
-        feats.append(x.reshape(x.shape[0], -1))
+        feats.append(x if metric == "dtw" else x.reshape(x.shape[0], -1))
         labels.append(y.to(dev).long())
-    if standardize:
+    if standardize and metric == "dtw":
+        C = feats[0].shape[2]
+        mean, scale = standard_scaler(feats[0].reshape(-1, C))
+        feats = [_standardize(f.reshape(-1, C), mean, scale).reshape(f.shape) for f in feats]
+    elif standardize:
         mean, scale = standard_scaler(feats[0])
         feats = [_standardize(f, mean, scale) for f in feats]
     n_classes = max(2, max(int(y.max()) + 1 if y.numel() else 0 for y in labels))
 
     def run(qi, q_group, x_group):
-        idx, dist = knn_search(feats[qi], feats[0], k, standardize=False, q_group=q_group, x_group=x_group)
+        if metric == "dtw":
+            idx, dist = dtw_search(feats[qi], feats[0], k, radius=radius, standardize=False, q_group=q_group,
+                                   x_group=x_group)
+        else:
+            idx, dist = knn_search(feats[qi], feats[0], k, standardize=False, q_group=q_group, x_group=x_group)
         pred, _ = knn_vote(idx, dist, labels[0], n_classes=n_classes, weights=weights)
         return {**_metrics(pred, labels[qi]), "idx": idx, "dist": dist, "pred": pred}
 

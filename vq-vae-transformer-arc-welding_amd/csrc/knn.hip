@@ -15,13 +15,15 @@
 //                      against its current k-th distance (a register); the rare winner is inserted into the query's
 //                      sorted list in LDS ([slot][query]: conflict-free).  Ascending j with a strict < is the
 //                      lexicographic (d, j) order inside a split.
-//   knn_merge_kernel   one wave per query: k selection passes over the splits' partial lists (splits * k candidates)
-//                      on 64-bit keys (order-preserving distance bits above j): the same (d, j) order, so the result
-//                      does not depend on the split count.  It also clamps the stored distance at 0 and widens idx.
+//   knn_merge_kernel   (knn_merge.h, shared with dtw.hip) one wave per query: k selection passes over the splits'
+//                      partial lists (splits * k candidates) on 64-bit keys (order-preserving distance bits above j):
+//                      the same (d, j) order, so the result does not depend on the split count.  It also clamps the
+//                      stored distance at 0 and widens idx.
 //
 // One (i, j) distance is always accumulated over all of D by one wave in one fixed order (pair_tile.h): its bits
 // depend on neither the grid nor the run.  No float atomics anywhere.
 #include "common.h"
+#include "knn_merge.h"
 #include "pair_tile.h"
 
 #include <math.h>
@@ -127,60 +129,6 @@ __global__ __launch_bounds__(KTHREADS, KCAP <= KNN_KCAP_SMALL ? 2 : 1) void knn_
   }
 }
 
-// f32 bits -> u32 with the same order as the floats (negatives reversed below the positives)
-__device__ __forceinline__ uint32_t knn_ord(float d) {
-  const uint32_t u = __float_as_uint(d);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float knn_unord(uint32_t o) {
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
-}
-
-__global__ __launch_bounds__(KTHREADS) void knn_merge_kernel(const float* __restrict__ ws_d,
-                                                             const int* __restrict__ ws_i, int64_t nq, int k,
-                                                             int splits, int64_t* __restrict__ idx,
-                                                             float* __restrict__ dist) {
-  const int lane = threadIdx.x & 63;
-  const int64_t qi = (int64_t)blockIdx.x * (KTHREADS / 64) + (threadIdx.x >> 6);
-  if (qi >= nq) return;   // wave-uniform
-  const int n = splits * k;
-  unsigned long long last = 0;
-  bool first = true;
-  for (int s = 0; s < k; ++s) {
-    unsigned long long best = ~0ull;
-    for (int c = lane; c < n; c += 64) {
-      const int sp = c / k, e = c - sp * k;
-      const int64_t o = ((int64_t)sp * nq + qi) * k + e;
-      const int j = ws_i[o];
-      if (j >= 0) {
-        const unsigned long long key = ((unsigned long long)knn_ord(ws_d[o]) << 32) | (uint32_t)j;
-        if ((first || key > last) && key < best) best = key;
-      }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const uint32_t lo = __shfl_xor((uint32_t)best, off, 64), hi = __shfl_xor((uint32_t)(best >> 32), off, 64);
-      const unsigned long long other = ((unsigned long long)hi << 32) | lo;
-      best = other < best ? other : best;
-    }
-    if (best == ~0ull) {   // fewer than s + 1 eligible rows: the tail is (-1, +inf)
-      if (lane == 0)
-        for (int r = s; r < k; ++r) {
-          idx[qi * k + r] = -1;
-          dist[qi * k + r] = __builtin_huge_valf();
-        }
-      return;
-    }
-    last = best;
-    first = false;
-    if (lane == 0) {
-      const float d = knn_unord((uint32_t)(best >> 32));
-      idx[qi * k + s] = (int64_t)(uint32_t)best;
-      dist[qi * k + s] = d > 0.f ? d : 0.f;   // the clamp is on the stored value only, never on the ranking
-    }
-  }
-}
-
 // The database is split so that a launch with few query tiles still fills the 256 CUs (about two workgroups each).
 int knn_auto_splits(int64_t nq, int64_t nx) {
   const int64_t qtiles = (nq + KQ - 1) / KQ, xtiles = (nx + KX - 1) / KX;
@@ -263,8 +211,9 @@ extern "C" int aw_knn(const float* q, int64_t nq, int64_t ldq, const float* x, i
 #undef KNN_SWEEP
   const int st2 = aw::check_launch("aw_knn (sweep)");
   if (st2 != AW_OK) return st2;
-  const int64_t mblocks = (nq + KTHREADS / 64 - 1) / (KTHREADS / 64);
+  const int64_t mblocks = knn_merge_blocks(nq);
   AW_REQUIRE(mblocks <= 0x7FFFFFFFll, "aw_knn: nq = %lld needs too many merge blocks", (long long)nq);
-  hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)mblocks), dim3(KTHREADS), 0, s, ws_d, ws_i, nq, k, sp, idx, dist);
+  hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)mblocks), dim3(KNN_MERGE_THREADS), 0, s, ws_d, ws_i, nq, k, sp,
+                     idx, dist);
   return aw::check_launch("aw_knn (merge)");
 }

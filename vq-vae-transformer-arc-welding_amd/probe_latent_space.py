@@ -17,6 +17,13 @@ neighbours.
 '<split>_idx' (n, k) int64, '<split>_dist' (n, k) f32 (squared distances; -1 / +inf past the eligible rows) and
 '<split>_pred' (n,) int64 per split.
 
+``--metric dtw`` (k-NN protocol, ``--dataset asimow`` only) replaces the sample-by-sample Euclidean distance of the raw
+cycles by dynamic time warping (arcweld.retrieve.dtw_search, csrc/dtw.hip): weld cycles differ in phase and duration,
+and 1-NN under DTW is the baseline a representation of time series has to beat.  ``--band F`` (0 <= F <= 1, default
+0.1) is the Sakoe-Chiba band as a fraction of the sequence length L = n_cycles * 200: radius = min(L - 1,
+floor(F * L)) samples, at most 224.  The scaler is then one mean and scale per channel.  ``--out`` gains "metric",
+"band" and "radius"; the distances of ``--neighbours-out`` are DTW costs.
+
 ``--protocol linear`` is the reference's other protocol, fit_lr: the same StandardScaler, then an L2-regularised
 logistic regression fitted on the train split (arcweld.retrieve.latent_linear_probe, csrc/logreg.hip), one per value
 of ``--C``, all in the same passes over the features; ``--tol`` and ``--max-iter`` bound the fit.  ``--out`` then
@@ -80,7 +87,45 @@ def parser():
                         "default 20000")
     p.add_argument('--gamma', type=gamma_arg, default="scale", help="svm: RBF width, a positive float or 'scale'")
     p.add_argument('--model-out', type=str, default="", help="linear, svm: .npz of the fitted model")
+    p.add_argument('--metric', choices=["euclidean", "dtw"], default="euclidean",
+                   help="knn: the distance; dtw (dynamic time warping) needs --dataset asimow")
+    p.add_argument('--band', type=float, default=None,
+                   help="knn, --metric dtw: the warping band as a fraction of the sequence length, 0..1, default 0.1")
     return p
+
+
+DEFAULT_BAND = 0.1
+
+
+def resolve_dtw(hparams):
+    """{} for the Euclidean metric, {"metric": "dtw", "band", "radius"} for --metric dtw; refuses --metric and --band
+    where they do not belong and values outside their ranges, before any file is read."""
+    if hparams.protocol != "knn":
+        if hparams.metric != "euclidean" or hparams.band is not None:
+            raise SystemExit("--metric and --band belong to --protocol knn")
+        return {}
+    if hparams.metric != "dtw":
+        if hparams.band is not None:
+            raise SystemExit("--band belongs to --metric dtw")
+        return {}
+    if hparams.dataset != "asimow":
+        raise SystemExit("--metric dtw warps the raw cycles and needs --dataset asimow: the latent vectors of "
+                         "--dataset latent_vq_vae are not time series")
+    band = DEFAULT_BAND if hparams.band is None else hparams.band
+    if not 0 <= band <= 1:
+        raise SystemExit("--band must lie in 0..1 (a fraction of the sequence length)")
+    if hparams.n_cycles < 1:
+        raise SystemExit("--n-cycles must be at least 1")
+    from arcweld.retrieve import MAX_DTW_LEN, MAX_DTW_WINDOW
+    L = hparams.n_cycles * 200
+    radius = min(L - 1, int(band * L))
+    if L > MAX_DTW_LEN:
+        raise SystemExit(f"--metric dtw holds sequences of at most {MAX_DTW_LEN} samples, --n-cycles "
+                         f"{hparams.n_cycles} gives {L}")
+    if 2 * radius + 1 > MAX_DTW_WINDOW:
+        raise SystemExit(f"--band {band:g} of {L} samples is a radius of {radius}, --metric dtw holds at most "
+                         f"{(MAX_DTW_WINDOW - 1) // 2}")
+    return dict(metric="dtw", band=band, radius=radius)
 
 
 PROTOCOL_DEFAULTS = {"linear": dict(C=[1.0], tol=1e-4, max_iter=1000), "svm": dict(C=[0.1], tol=1e-3, max_iter=20000)}
@@ -186,6 +231,7 @@ def main_svm(hparams):
 
 
 def main(hparams):
+    dtw = resolve_dtw(hparams)
     if hparams.dataset == "latent_vq_vae":
         require_checkpoint(hparams.vqvae_model, "--vqvae-model")
     if hparams.n_cycles < 1:
@@ -206,10 +252,11 @@ def main(hparams):
     vqvae = load_vqvae(hparams.vqvae_model, dev) if hparams.dataset == "latent_vq_vae" else None
     res = latent_knn_probe(load_splits(hparams, dev), hparams.n_cycles, k=hparams.k, dataset=hparams.dataset,
                            vqvae=vqvae, weights=hparams.weights, standardize=not hparams.no_standardize,
-                           loo=hparams.loo, groups=load_groups(hparams.data_npz))
+                           loo=hparams.loo, groups=load_groups(hparams.data_npz),
+                           **({"metric": "dtw", "radius": dtw["radius"]} if dtw else {}))
     summary = {name: {m: r[m] for m in METRICS} for name, r in res.items()}
     summary.update(k=hparams.k, weights=hparams.weights, dataset=hparams.dataset,
-                   standardize=not hparams.no_standardize, n_cycles=hparams.n_cycles)
+                   standardize=not hparams.no_standardize, n_cycles=hparams.n_cycles, **dtw)
     with open(hparams.out, "w") as f:
         json.dump(summary, f, indent=1, sort_keys=True)
     if hparams.neighbours_out:
