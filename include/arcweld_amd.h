@@ -977,6 +977,51 @@ int aw_svm_smo(const float* k, int n, int64_t ldk, const int* y, const double* C
                double* alpha, double* grad, int64_t* n_iter, double* gap, void* stream);
 int aw_svm_describe(int* threads, int* rows_per_thread, int* max_n, int* max_p);
 
+/* ------------------------------------------------------------------------------------------------ TS2Vec encoder
+ * The eval forward of the TS2Vec baseline's dilated-convolution encoder (arcweld.ts2vec.TSEncoder.encode; the
+ * reference's model/ts2vec/encoder.py and dilated_conv.py), exact f32.  Activations are row-major (batch * T, C) f32:
+ * row b * T + t holds the C channels of time step t of sequence b, rows C floats apart, 16-byte aligned bases.
+ *
+ * aw_ts_input_fc: out[r, h] = bias[h] + sum_c x[r, c] * w[h, c] (an in-order fmaf chain from the bias; w is
+ *   (hidden, cin) as nn.Linear stores it) and out_gelu = gelu(out), the exact erf GELU.  A row of x with a NaN in any
+ *   channel, and a row whose mask byte is 0 (mask: rows bytes, optional), is all zeros in both outputs: the zeroing
+ *   before and after the reference's input_fc, bias included.  x is only read.
+ * aw_ts_conv: one dilated convolution of `taps` = 3 taps (or the pointwise projection, taps = 1) as a GEMM on
+ *   v_mfma_f32_32x32x2_f32 (bit for bit an fmaf chain):
+ *       acc[b, t, :] = sum_{k < taps} W_k . in[b, t + (k - taps / 2) * dilation, :],
+ *   w is (taps, cout, cin): tap k of torch's (cout, cin, taps) weight, re-laid-out once by the host.  A tap whose
+ *   source step lies outside [0, T) of ITS OWN sequence contributes nothing: every operand load goes through a buffer
+ *   descriptor that spans one sequence, so no row of a neighbouring sequence is ever read.  A workgroup owns
+ *   128 time steps x 64 output channels of one sequence and skips a tap that is dead for all of its rows (all but the
+ *   centre tap once dilation >= T): dead taps are not multiplied as zeros.
+ *   Epilogue: v = fl(fl(acc + bias) + resid) (resid (batch * T, cout), optional); out = v and out_gelu = gelu(v), each
+ *   optional.  pool (batch, cout), optional: pool[b, :] = max over t of v[b, t, :] -- a maximum per workgroup into
+ *   pool_ws, then a second small pass over the time tiles; max does not round, so the result has the bits of the
+ *   maximum of `out` whatever the order.  pool_ws needs aw_ts_pool_workspace(batch, T, cout) bytes.
+ *   A sequence's values depend only on its own rows, T and the weights: not on batch, its position in it, or the run.
+ * The order of one output element's sum: taps ascending (dead ones skipped), channels in chunks of 32 ascending, in a
+ * chunk MFMA step 4 g + s multiplies channels 8 g + s (lanes 0..31) and 8 g + 4 + s (lanes 32..63).
+ * Limits (AW_ERR_ARG and no launch beyond them): T in 1..AW_TS_MAX_T, cin (of aw_ts_input_fc) in 1..AW_TS_MAX_CIN,
+ * every width (hidden, cin / cout of aw_ts_conv) a multiple of 16 in 16..AW_TS_MAX_WIDTH, taps 1 or 3, dilation in
+ * 1..AW_TS_MAX_DILATION, batch in 0..AW_TS_MAX_BATCH per call, rows in 0..2^31 - 1; a NULL or misaligned operand; no
+ * output at all.  batch == 0 / rows == 0: AW_OK, nothing launched.  Neither call allocates or synchronises.
+ * Working set: beside the result the host keeps 5 hidden-wide and 2 output-wide activation buffers per row,
+ * 4 T (5 hidden + 2 cout) bytes per sequence, and cuts the batch into chunks so that they stay within
+ * AW_TS_WORKSPACE_BYTES (256 MiB; one sequence at the limits needs 56 MiB). */
+#define AW_TS_MAX_T 4096
+#define AW_TS_MAX_CIN 8
+#define AW_TS_MAX_WIDTH 512
+#define AW_TS_MAX_DILATION 1073741824
+#define AW_TS_MAX_BATCH 65535
+#define AW_TS_WORKSPACE_BYTES 268435456
+int aw_ts_input_fc(const float* x, const void* mask, const float* w, const float* bias, int64_t rows, int cin,
+                   int hidden, float* out, float* out_gelu, void* stream);
+int64_t aw_ts_pool_workspace(int batch, int T, int cout);
+int aw_ts_conv(const float* in, const float* w, const float* bias, const float* resid, int batch, int T, int cin,
+               int cout, int taps, int dilation, float* out, float* out_gelu, float* pool, float* pool_ws,
+               void* stream);
+int aw_ts_describe(int* tile_t, int* tile_c, int* chunk_c);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1113,6 +1113,92 @@ def svm_smo(k, y, C, tol, max_iter, alpha=None, grad=None, n_iter=None, gap=None
     return alpha, grad, n_iter, gap
 
 
+def ts_describe():
+    """aw_ts_describe: (tile_t, tile_c, chunk_c) of the TS2Vec convolution kernel: time steps and output channels per
+    workgroup, input channels per chunk (the tests aim at the tile edges)."""
+    v = [ctypes.c_int(0) for _ in range(3)]
+    call("aw_ts_describe", *[ctypes.byref(c) for c in v])
+    return tuple(int(c.value) for c in v)
+
+
+def _ts_act(t, nm, rows, width, who, dev):
+    if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (rows, width) or not t.is_contiguous()
+                          or t.device != dev):
+        raise nat.NativeError(f"{who}: {nm} must be a contiguous float32 tensor of shape {(rows, width)} on the "
+                              f"input's device, got {t.dtype} {tuple(t.shape)}")
+
+
+def ts_input_fc(x, w, bias, mask=None, out=None, out_gelu=None, stream=None):
+    """aw_ts_input_fc: the TS2Vec encoder's input projection with its NaN / mask zeroing.  x (rows, cin) f32 (NaN =
+    missing), w (hidden, cin), bias (hidden,), mask (rows,) uint8 or bool (0 = zero the row), all contiguous on one
+    device.  Writes out and out_gelu (rows, hidden) f32 -- the projected rows and their exact-erf GELU -- and returns
+    them; x is not modified.  The ranges of cin and hidden are the library's to refuse."""
+    who = "ts_input_fc"
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda:
+        raise nat.NativeError(f"{who}: x must be a contiguous (rows, cin) float32 device tensor")
+    rows, cin = x.shape
+    dev = x.device
+    if w.dim() != 2 or w.shape[1] != cin or w.dtype != torch.float32 or not w.is_contiguous() or w.device != dev:
+        raise nat.NativeError(f"{who}: w must be a contiguous (hidden, {cin}) float32 tensor on x's device")
+    hidden = w.shape[0]
+    if bias.dtype != torch.float32 or tuple(bias.shape) != (hidden,) or not bias.is_contiguous() or bias.device != dev:
+        raise nat.NativeError(f"{who}: bias must be a contiguous float32 tensor of {hidden} elements on x's device")
+    if mask is not None:
+        if (mask.dtype not in (torch.uint8, torch.bool) or tuple(mask.shape) != (rows,) or not mask.is_contiguous()
+                or mask.device != dev):
+            raise nat.NativeError(f"{who}: mask must be a contiguous uint8 / bool tensor of {rows} elements on x's "
+                                  f"device")
+    if out is None:
+        out = torch.empty((rows, hidden), dtype=torch.float32, device=dev)
+    if out_gelu is None:
+        out_gelu = torch.empty((rows, hidden), dtype=torch.float32, device=dev)
+    _ts_act(out, "out", rows, hidden, who, dev)
+    _ts_act(out_gelu, "out_gelu", rows, hidden, who, dev)
+    call("aw_ts_input_fc", ptr(x), ptr(mask), ptr(w), ptr(bias), rows, cin, hidden, ptr(out), ptr(out_gelu),
+         stream_ptr(stream))
+    return out, out_gelu
+
+
+def ts_conv(x, w, bias, batch, T, dilation, resid=None, out=None, out_gelu=None, pool=None, stream=None):
+    """aw_ts_conv: one dilated convolution of the TS2Vec encoder over (batch * T, cin) f32 activations (row b * T + t
+    = step t of sequence b).  w (taps, cout, cin) f32, taps 3 or 1 (the pointwise projection), bias (cout,).
+    v = conv + bias (+ resid (batch * T, cout)); out = v, out_gelu = gelu(v), pool (batch, cout) = max over t of v: the
+    caller passes the tensors it wants written, at least one.  No tap reads another sequence's rows.  The ranges of
+    T, the widths, taps, dilation and batch are the library's to refuse (NativeError, nothing launched)."""
+    who = "ts_conv"
+    batch, T, dilation = int(batch), int(T), int(dilation)
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous() or not x.is_cuda or x.shape[0] != batch * T:
+        raise nat.NativeError(f"{who}: the input must be a contiguous (batch * T = {batch * T}, cin) float32 device "
+                              f"tensor, got {x.dtype} {tuple(x.shape)}")
+    rows, cin = x.shape
+    dev = x.device
+    if w.dim() != 3 or w.shape[2] != cin or w.dtype != torch.float32 or not w.is_contiguous() or w.device != dev:
+        raise nat.NativeError(f"{who}: w must be a contiguous (taps, cout, {cin}) float32 tensor on the input's device")
+    taps, cout = w.shape[0], w.shape[1]
+    if bias.dtype != torch.float32 or tuple(bias.shape) != (cout,) or not bias.is_contiguous() or bias.device != dev:
+        raise nat.NativeError(f"{who}: bias must be a contiguous float32 tensor of {cout} elements on the input's "
+                              f"device")
+    _ts_act(resid, "resid", rows, cout, who, dev)
+    _ts_act(out, "out", rows, cout, who, dev)
+    _ts_act(out_gelu, "out_gelu", rows, cout, who, dev)
+    _ts_act(pool, "pool", batch, cout, who, dev)
+    ws = None
+    if pool is not None:
+        lib = nat.load()
+        ws_bytes = lib.aw_ts_pool_workspace(batch, T, cout)
+        if ws_bytes < 0:
+            raise nat.NativeError(f"aw_ts_pool_workspace failed ({ws_bytes}): "
+                                  f"{lib.aw_last_error().decode(errors='replace')}")
+        ws = torch.empty(max(ws_bytes // 4, 4), dtype=torch.float32, device=dev)
+    live = sum(1 for k in range(taps) if taps == 1 or abs(k - 1) * dilation < T)
+    _maybe_timed(stream, "ts_conv", 2.0 * rows * cout * cin * live, lambda s: call(
+        "aw_ts_conv", ptr(x), ptr(w), ptr(bias), ptr(resid), batch, T, cin, cout, taps, dilation, ptr(out),
+        ptr(out_gelu), ptr(pool), ptr(ws), s),
+        info=lambda: (f"ts_conv_kernel taps={taps} cin={cin} cout={cout} d={dilation}",
+                      4.0 * rows * (cin + cout * sum(t is not None for t in (resid, out, out_gelu)))))
+    return out, out_gelu, pool
+
+
 # ------------------------------------------------------------------------------------------ layouts
 def patchify(x, P, out, stream=None):
     B, L, C = x.shape

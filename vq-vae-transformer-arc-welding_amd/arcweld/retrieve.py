@@ -9,6 +9,7 @@ and answers "which training welds does this sequence look like".
   knn_search        (idx, dist) of the k nearest database rows per query, optionally standardised
   knn_vote          class votes of the neighbours' labels -> (pred, votes); plain torch on the inputs' device
   latent_knn_probe  train split = database, val / test = queries: accuracy, per-class accuracy, F1 and the neighbours
+                    (dataset "ts2vec": of the TS2Vec baseline's pooled representations, arcweld.ts2vec)
 
   dtw_search        the same under banded dynamic time warping of (n, L, C) sequences (arcweld.kernels.dtw_knn,
                     csrc/dtw.hip): the strong baseline for raw weld cycles, which differ in phase and duration
@@ -81,6 +82,27 @@ def _device_of(*tensors):
         if t.is_cuda:
             return t.device
     return torch.device("cuda", torch.cuda.current_device())
+
+
+_DATASETS = ("asimow", "latent_vq_vae", "ts2vec")
+
+
+def _check_ts2vec(dataset, ts2vec):
+    if dataset == "ts2vec" and (ts2vec is None or not callable(getattr(ts2vec, "encode", None))):
+        raise ValueError("ts2vec: dataset ts2vec needs the TS2Vec encoder (arcweld.ts2vec.TSEncoder or "
+                         "model.ts2vec.TS2Vec)")
+    if dataset != "ts2vec" and ts2vec is not None:
+        raise ValueError(f"ts2vec: belongs to dataset 'ts2vec', got an encoder with dataset {dataset!r}")
+
+
+def _ts2vec_features(ts2vec, x):
+    """The reference's eval_classification features: encode(x, encoding_window='full_series') of the (n, n_cycles *
+    window, C) split, (n, output_dims) f32 on x's device (model.ts2vec.TS2Vec returns an array, TSEncoder a tensor)."""
+    f = ts2vec.encode(x, encoding_window="full_series")
+    f = torch.as_tensor(f).to(x.device, torch.float32)
+    if f.dim() != 2 or f.shape[0] != x.shape[0]:
+        raise ValueError(f"ts2vec: encode returned shape {tuple(f.shape)} for {x.shape[0]} sequences")
+    return f
 
 
 @torch.no_grad()
@@ -274,12 +296,15 @@ def _metrics(pred, target):
 
 @torch.no_grad()
 def latent_knn_probe(splits, n_cycles, k=1, dataset="latent_vq_vae", vqvae=None, weights="uniform", standardize=True,
-                     loo=False, groups=None, window=200, metric="euclidean", radius=None):
+                     loo=False, groups=None, window=200, metric="euclidean", radius=None, ts2vec=None):
     """k-NN probe of a feature space: the train split is the database, val and test are the queries.
 
     splits: [(x (n, n_cycles*window, C), labels (n,))] for train / val / test, as ClassificationDataModule takes them.
     The features are what that module would feed the GRU, flattened per sequence: the windows themselves ("asimow") or
-    the frozen VQ-VAE's latent vectors (arcweld.data.latent_vectors, "latent_vq_vae").  Returns {"val": r, "test": r},
+    the frozen VQ-VAE's latent vectors (arcweld.data.latent_vectors, "latent_vq_vae"), or -- dataset "ts2vec" with
+    ts2vec= an arcweld.ts2vec.TSEncoder or a model.ts2vec.TS2Vec -- the learned baseline's pooled representations,
+    encode(x, encoding_window='full_series') of each split: the reference's eval_classification.  The linear and the
+    SVM probe take the same two arguments.  Returns {"val": r, "test": r},
     r = {acc, acc_good, acc_bad, f1: floats on the GRU path's scale (model.classification_model's metric functions),
     idx, dist (n, k), pred (n,): device tensors}.  loo=True adds "train_loo": the train split against itself, each row
     excluded from its own neighbours -- or, with groups["train"], everything of its own group (leave-one-run-out).
@@ -289,10 +314,13 @@ def latent_knn_probe(splits, n_cycles, k=1, dataset="latent_vq_vae", vqvae=None,
     the raw (n, n_cycles * window, C) sequences under dynamic time warping (dtw_search) in a band of `radius` samples
     (None: unconstrained); standardize is then dtw_search's per-channel scaler, fitted on the train split; dist is
     the DTW cost.  Voting, metrics, loo and groups are the same.  radius belongs to metric "dtw"."""
-    if dataset not in ("asimow", "latent_vq_vae"):
+    if dataset not in _DATASETS:
         raise ValueError(f"dataset: expected 'asimow' or 'latent_vq_vae', got {dataset!r}")
     if metric not in ("euclidean", "dtw"):
         raise ValueError(f"metric: expected 'euclidean' or 'dtw', got {metric!r}")
+    if metric == "dtw" and dataset == "ts2vec":
+        raise ValueError("metric: 'dtw' warps the time axis of the raw cycles and needs dataset 'asimow'; the rows of "
+                         "dataset 'ts2vec' are pooled representations, not time series")
     if metric == "dtw" and dataset != "asimow":
         raise ValueError("metric: 'dtw' warps the time axis of the raw cycles and needs dataset 'asimow'; the rows of "
                          "dataset 'latent_vq_vae' are (n_cycles, 1024)-shaped latent vectors, not time series")
@@ -300,6 +328,7 @@ def latent_knn_probe(splits, n_cycles, k=1, dataset="latent_vq_vae", vqvae=None,
         raise ValueError(f"radius: belongs to metric 'dtw', got {radius!r} with metric {metric!r}")
     if dataset == "latent_vq_vae" and vqvae is None:
         raise ValueError("vqvae: dataset latent_vq_vae needs the frozen VQ-VAE")
+    _check_ts2vec(dataset, ts2vec)
     if isinstance(n_cycles, bool) or not isinstance(n_cycles, int) or n_cycles < 1:
         raise ValueError(f"n_cycles: expected a positive int, got {n_cycles!r}")
     k = _check_k(k)
@@ -341,6 +370,8 @@ def latent_knn_probe(splits, n_cycles, k=1, dataset="latent_vq_vae", vqvae=None,
         if dataset == "latent_vq_vae":
             from .data import latent_vectors
             x = latent_vectors(vqvae, x, n_cycles, window)
+        elif dataset == "ts2vec":
+            x = _ts2vec_features(ts2vec, x)
         feats.append(x if metric == "dtw" else x.reshape(x.shape[0], -1))
         labels.append(y.to(dev).long())
     if standardize and metric == "dtw":
@@ -610,7 +641,7 @@ def stratified_subsample(labels, max_samples, seed=0):
 
 @torch.no_grad()
 def latent_linear_probe(splits, n_cycles, C=(1.0,), dataset="latent_vq_vae", vqvae=None, standardize=True, tol=1e-4,
-                        max_iter=1000, max_samples=100000, window=200, seed=0):
+                        max_iter=1000, max_samples=100000, window=200, seed=0, ts2vec=None):
     """Linear probe of a feature space: the reference's eval_protocol='linear' (fit_lr) on the features of
     latent_knn_probe.  A logistic regression per C is fitted on the train split (logreg_fit; above max_samples rows on
     a seeded stratified subsample, as fit_lr does) and scored on val and test.
@@ -619,10 +650,11 @@ def latent_linear_probe(splits, n_cycles, C=(1.0,), dataset="latent_vq_vae", vqv
     the GRU path's val/f1_score_mean; ties to the smaller C), "val" / "test": m at that C plus "pred" (n,) int64 and
     "decision" (n, n_problems_per_C) f32 device tensors, "fit": logreg_fit's dict, "converged", "n_iter" (per C, over
     its problems)}, m = {acc, acc_good, acc_bad, f1} as latent_knn_probe reports them."""
-    if dataset not in ("asimow", "latent_vq_vae"):
+    if dataset not in _DATASETS:
         raise ValueError(f"dataset: expected 'asimow' or 'latent_vq_vae', got {dataset!r}")
     if dataset == "latent_vq_vae" and vqvae is None:
         raise ValueError("vqvae: dataset latent_vq_vae needs the frozen VQ-VAE")
+    _check_ts2vec(dataset, ts2vec)
     if isinstance(n_cycles, bool) or not isinstance(n_cycles, int) or n_cycles < 1:
         raise ValueError(f"n_cycles: expected a positive int, got {n_cycles!r}")
     Cs = _check_C(C)
@@ -656,6 +688,8 @@ def latent_linear_probe(splits, n_cycles, C=(1.0,), dataset="latent_vq_vae", vqv
         if dataset == "latent_vq_vae":
             from .data import latent_vectors
             x = latent_vectors(vqvae, x, n_cycles, window)
+        elif dataset == "ts2vec":
+            x = _ts2vec_features(ts2vec, x)
         feats.append(x.reshape(x.shape[0], -1))
         labels.append(y.to(dev).long())
     n_classes = max(2, max(int(y.max()) + 1 if y.numel() else 0 for y in labels))
@@ -886,7 +920,8 @@ def svm_predict(fit, queries, decision=None):
 
 @torch.no_grad()
 def latent_svm_probe(splits, n_cycles, C=(0.1,), gamma="scale", dataset="latent_vq_vae", vqvae=None,
-                     standardize=False, tol=1e-3, max_iter=_SVM_MAX_ITER, max_samples=20000, window=200, seed=42):
+                     standardize=False, tol=1e-3, max_iter=_SVM_MAX_ITER, max_samples=20000, window=200, seed=42,
+                     ts2vec=None):
     """RBF-SVM probe of a feature space: the reference's eval_protocol='svm' (fit_svm) on the features of
     latent_knn_probe.  A support-vector classifier per C is fitted on the train split (svm_fit; above max_samples rows
     on a seeded stratified subsample, as fit_svm does above 20 000) and scored on val and test.
@@ -898,10 +933,11 @@ def latent_svm_probe(splits, n_cycles, C=(0.1,), gamma="scale", dataset="latent_
     Not offered, and refused or left out on purpose: fit_svm's small-set branch (a train split of fewer than 50 rows,
     or fewer than 5 per class, which it fits with C = inf) is a ValueError; its 5-fold cross-validation is skipped, the
     grid having one point; the subsample is stratified_subsample's, not scikit-learn's rows."""
-    if dataset not in ("asimow", "latent_vq_vae"):
+    if dataset not in _DATASETS:
         raise ValueError(f"dataset: expected 'asimow' or 'latent_vq_vae', got {dataset!r}")
     if dataset == "latent_vq_vae" and vqvae is None:
         raise ValueError("vqvae: dataset latent_vq_vae needs the frozen VQ-VAE")
+    _check_ts2vec(dataset, ts2vec)
     if isinstance(n_cycles, bool) or not isinstance(n_cycles, int) or n_cycles < 1:
         raise ValueError(f"n_cycles: expected a positive int, got {n_cycles!r}")
     Cs = _check_C(C)
@@ -941,6 +977,8 @@ def latent_svm_probe(splits, n_cycles, C=(0.1,), gamma="scale", dataset="latent_
         if dataset == "latent_vq_vae":
             from .data import latent_vectors
             x = latent_vectors(vqvae, x, n_cycles, window)
+        elif dataset == "ts2vec":
+            x = _ts2vec_features(ts2vec, x)
         feats.append(x.reshape(x.shape[0], -1))
         labels.append(y.to(dev).long())
     n_classes = max(2, max(int(y.max()) + 1 if y.numel() else 0 for y in labels))

@@ -12,6 +12,11 @@ with optional '<split>_groups' (integer ids, e.g. the welding run): a query neve
 ``--loo`` adds the train split against itself, each sequence (or, with 'train_groups', each group) left out of its own
 neighbours.
 
+``--dataset ts2vec --ts2vec-model PATH`` probes the learned baseline the protocols were written for: PATH is a checkpoint
+written by the reference's ``TS2Vec.save`` (widths and depth are read from its shapes), the features are its pooled
+representations ``encode(x, encoding_window='full_series')`` of every sequence (arcweld.ts2vec, csrc/ts2vec.hip): the
+reference's eval_classification.  All three protocols take it; ``--out`` keeps its keys, "dataset" reads "ts2vec".
+
 ``--out`` receives the metrics as JSON: {"val" / "test" / "train_loo": {"acc", "acc_good", "acc_bad", "f1"}, "k",
 "weights", "dataset", "standardize", "n_cycles"}.  ``--neighbours-out`` (optional) receives an .npz with
 '<split>_idx' (n, k) int64, '<split>_dist' (n, k) f32 (squared distances; -1 / +inf past the eligible rows) and
@@ -63,7 +68,9 @@ def parser():
     p = argparse.ArgumentParser(description='Probe-Latent-Space')
     p.add_argument('--vqvae-model', type=str, help='Path of the VQ-VAE checkpoint',
                    default="model_checkpoints/VQ-VAE-Patch/vq_vae_patch_best_02.ckpt")
-    p.add_argument('--dataset', choices=["latent_vq_vae", "asimow"], default="latent_vq_vae")
+    p.add_argument('--dataset', choices=["latent_vq_vae", "asimow", "ts2vec"], default="latent_vq_vae")
+    p.add_argument('--ts2vec-model', type=str, default="",
+                   help="--dataset ts2vec: a checkpoint written by the reference's TS2Vec.save")
     p.add_argument('--n-cycles', type=int, help='Number of cycles', default=5)
     p.add_argument('--k', type=int, help='Neighbours per query', default=1)
     p.add_argument('--weights', choices=["uniform", "distance"], default="uniform")
@@ -108,6 +115,9 @@ def resolve_dtw(hparams):
         if hparams.band is not None:
             raise SystemExit("--band belongs to --metric dtw")
         return {}
+    if hparams.dataset == "ts2vec":
+        raise SystemExit("--metric dtw warps the raw cycles and needs --dataset asimow: the pooled representations of "
+                         "--dataset ts2vec are not time series")
     if hparams.dataset != "asimow":
         raise SystemExit("--metric dtw warps the raw cycles and needs --dataset asimow: the latent vectors of "
                          "--dataset latent_vq_vae are not time series")
@@ -153,6 +163,18 @@ def resolve_fit_args(hparams):
     return C, tol, max_iter
 
 
+def load_ts2vec(hparams, dev):
+    """The TS2Vec encoder of --ts2vec-model on the device for --dataset ts2vec (widths and depth from the
+    checkpoint's shapes), else None."""
+    if hparams.dataset != "ts2vec":
+        return None
+    from arcweld.ts2vec import load_checkpoint
+    try:
+        return load_checkpoint(hparams.ts2vec_model, dev)
+    except (ValueError, RuntimeError, KeyError) as e:
+        raise SystemExit(f"--ts2vec-model: {hparams.ts2vec_model!r} is not a TS2Vec checkpoint ({e})") from None
+
+
 def load_groups(path):
     """{'train' / 'val' / 'test': ids} for the '<split>_groups' arrays the .npz holds (none: {})."""
     if not path:
@@ -175,8 +197,10 @@ def main_linear(hparams):
     from train_transformer_mtasks import load_splits, load_vqvae
     dev = torch.device("cuda", torch.cuda.current_device())
     vqvae = load_vqvae(hparams.vqvae_model, dev) if hparams.dataset == "latent_vq_vae" else None
+    ts2vec = load_ts2vec(hparams, dev)
     res = latent_linear_probe(load_splits(hparams, dev), hparams.n_cycles, C=C, dataset=hparams.dataset,
-                              vqvae=vqvae, standardize=not hparams.no_standardize, tol=tol, max_iter=max_iter)
+                              vqvae=vqvae, standardize=not hparams.no_standardize, tol=tol, max_iter=max_iter,
+                              ts2vec=ts2vec)
     summary = {name: {m: res[name][m] for m in METRICS} for name in ("val", "test")}
     summary.update(per_C=res["per_C"], C_selected=res["C_selected"], protocol="linear", dataset=hparams.dataset,
                    standardize=not hparams.no_standardize, n_cycles=hparams.n_cycles, converged=res["converged"],
@@ -205,10 +229,11 @@ def main_svm(hparams):
     from train_transformer_mtasks import load_splits, load_vqvae
     dev = torch.device("cuda", torch.cuda.current_device())
     vqvae = load_vqvae(hparams.vqvae_model, dev) if hparams.dataset == "latent_vq_vae" else None
+    ts2vec = load_ts2vec(hparams, dev)
     try:
         res = latent_svm_probe(load_splits(hparams, dev), hparams.n_cycles, C=C, gamma=hparams.gamma,
                                dataset=hparams.dataset, vqvae=vqvae, standardize=hparams.standardize, tol=tol,
-                               max_iter=max_iter)
+                               max_iter=max_iter, ts2vec=ts2vec)
     except ValueError as e:
         raise SystemExit(f"--protocol svm: {e}") from None
     summary = {name: {m: res[name][m] for m in METRICS} for name in ("val", "test")}
@@ -234,6 +259,12 @@ def main(hparams):
     dtw = resolve_dtw(hparams)
     if hparams.dataset == "latent_vq_vae":
         require_checkpoint(hparams.vqvae_model, "--vqvae-model")
+    if hparams.dataset == "ts2vec":
+        if not hparams.ts2vec_model or not os.path.exists(hparams.ts2vec_model):
+            raise SystemExit(f"--ts2vec-model: checkpoint {hparams.ts2vec_model!r} not found -- --dataset ts2vec "
+                             "probes a trained TS2Vec encoder (the file the reference's TS2Vec.save writes)")
+    elif hparams.ts2vec_model:
+        raise SystemExit("--ts2vec-model belongs to --dataset ts2vec")
     if hparams.n_cycles < 1:
         raise SystemExit("--n-cycles must be at least 1")
     if hparams.protocol == "linear":
@@ -250,9 +281,10 @@ def main(hparams):
     from train_transformer_mtasks import load_splits, load_vqvae
     dev = torch.device("cuda", torch.cuda.current_device())
     vqvae = load_vqvae(hparams.vqvae_model, dev) if hparams.dataset == "latent_vq_vae" else None
+    ts2vec = load_ts2vec(hparams, dev)
     res = latent_knn_probe(load_splits(hparams, dev), hparams.n_cycles, k=hparams.k, dataset=hparams.dataset,
                            vqvae=vqvae, weights=hparams.weights, standardize=not hparams.no_standardize,
-                           loo=hparams.loo, groups=load_groups(hparams.data_npz),
+                           loo=hparams.loo, groups=load_groups(hparams.data_npz), ts2vec=ts2vec,
                            **({"metric": "dtw", "radius": dtw["radius"]} if dtw else {}))
     summary = {name: {m: r[m] for m in METRICS} for name, r in res.items()}
     summary.update(k=hparams.k, weights=hparams.weights, dataset=hparams.dataset,
