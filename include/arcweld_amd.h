@@ -1022,6 +1022,46 @@ int aw_ts_conv(const float* in, const float* w, const float* bias, const float* 
                void* stream);
 int aw_ts_describe(int* tile_t, int* tile_c, int* chunk_c);
 
+/* ------------------------------------------------------------------------------------------------ TS2Vec loss
+ * The hierarchical contrastive loss of TS2Vec training (arcweld.ts2vec.hierarchical_contrastive_loss; the reference's
+ * model/ts2vec/losses.py), f32.  Both of its terms are the paired InfoNCE over groups: a group is 2 n rows of c
+ * floats, rows 0..n-1 from z1 and rows n..2n-1 from z2; row r of group g of either tensor starts at
+ * g * group_stride + r * row_stride floats.  With S = Z Z^T within a group and p(i) = (i + n) mod 2n,
+ *     lse[g, i] = log sum_{j != i} exp S_ij,      row_loss[g, i] = lse[g, i] - S_{i, p(i)}
+ * (lse and row_loss: (groups, 2 n) f32, contiguous).  The temporal term of (B, T, C) inputs is groups = B, n = T,
+ * group_stride = T C, row_stride = C; the instance term is groups = T, n = B, group_stride = C, row_stride = T C.
+ * No similarity is written to memory: the working set is the inputs and two floats per row.
+ *
+ * aw_nce_rows_fwd: lse and row_loss.  One row's value is accumulated in one fixed order over the group's rows (tiles
+ *   of 128 rows of z1, then of z2; within a tile per lane, then a fixed merge): its bits depend on neither the number
+ *   of groups, the group's position, nor the run.  n == 1 gives row_loss == 0 exactly.  No atomics.  Groups of
+ *   2 n <= 128 rows are packed, 4, 2 or 1 to a workgroup in slots of 32, 64 or 128 rows; the slot a group lands in
+ *   does not change its bits either.
+ * aw_nce_rows_bwd: with the forward's lse,
+ *     dz_i (+)= scale * [ sum_{j != i} (exp(S_ij - lse_i) + exp(S_ij - lse_j)) z_j  -  2 z_p(i) ],
+ *   the gradient of scale * sum of row_loss; dz1 / dz2 are addressed as z1 / z2.  accumulate != 0 adds to what dz
+ *   holds, 0 overwrites it.  Every element has one owning thread: no atomics, the same bits every run.
+ * aw_ts_pool2_fwd: out[b, t, :] = max(in[b, 2 t, :], in[b, 2 t + 1, :]) for t < T / 2 (in (batch, T, c), out
+ *   (batch, T / 2, c), contiguous): torch's max_pool1d(kernel 2, stride 2); an odd last step is dropped.
+ * aw_ts_pool2_bwd: din[b, 2 t + k, :] += dout[b, t, :] at the k the forward took (recomputed from `in`; the first
+ *   step on a tie, as torch does); the other step and an odd last step keep what they hold.
+ * Limits (AW_ERR_ARG and no launch beyond them): c a multiple of 16 in 16..AW_NCE_MAX_WIDTH, n >= 1 with
+ * 2 n <= AW_NCE_MAX_ROWS, groups in 0..AW_NCE_MAX_GROUPS per call, row_stride a multiple of 4 in c..2^22 - 1,
+ * group_stride a non-negative multiple of 4; the pools: T in 2..AW_TS_MAX_T, batch in 0..AW_TS_MAX_BATCH; a NULL or
+ * a not 16-byte aligned operand.  groups == 0 / batch == 0: AW_OK, nothing launched.  No call allocates or
+ * synchronises. */
+#define AW_NCE_MAX_ROWS 8192
+#define AW_NCE_MAX_GROUPS 65535
+#define AW_NCE_MAX_WIDTH 512
+int aw_nce_rows_fwd(const float* z1, const float* z2, int groups, int n, int c, int64_t group_stride,
+                    int64_t row_stride, float* lse, float* row_loss, void* stream);
+int aw_nce_rows_bwd(const float* z1, const float* z2, int groups, int n, int c, int64_t group_stride,
+                    int64_t row_stride, const float* lse, float scale, float* dz1, float* dz2, int accumulate,
+                    void* stream);
+int aw_nce_describe(int* tile_rows, int* chunk_c, int* slab_c);
+int aw_ts_pool2_fwd(const float* in, int batch, int T, int c, float* out, void* stream);
+int aw_ts_pool2_bwd(const float* in, const float* dout, int batch, int T, int c, float* din, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

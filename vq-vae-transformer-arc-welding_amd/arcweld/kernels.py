@@ -1199,6 +1199,141 @@ def ts_conv(x, w, bias, batch, T, dilation, resid=None, out=None, out_gelu=None,
     return out, out_gelu, pool
 
 
+# ------------------------------------------------------------------------------------------ TS2Vec loss
+NCE_MAX_ROWS, NCE_MAX_GROUPS, NCE_MAX_WIDTH = nat.AW_NCE_MAX_ROWS, nat.AW_NCE_MAX_GROUPS, nat.AW_NCE_MAX_WIDTH
+NCE_LAYOUTS = ("temporal", "instance")
+
+
+def nce_describe():
+    """aw_nce_describe: (rows per tile, dims per chunk, output columns per backward slab) of the loss kernels."""
+    v = [ctypes.c_int(0) for _ in range(3)]
+    call("aw_nce_describe", *[ctypes.byref(c) for c in v])
+    return tuple(int(c.value) for c in v)
+
+
+def _nce_geometry(z1, z2, layout, who):
+    """(groups, n, c, group stride, row stride) of the paired InfoNCE over (B, T, C) inputs; what the library would
+    refuse is a ValueError here, before any launch (and before the device is looked at)."""
+    if layout not in NCE_LAYOUTS:
+        raise ValueError(f"{who}: layout must be one of {NCE_LAYOUTS}, got {layout!r}")
+    for nm, z in (("z1", z1), ("z2", z2)):
+        if not isinstance(z, torch.Tensor) or z.dim() != 3 or z.dtype != torch.float32:
+            raise ValueError(f"{who}: {nm} must be a (B, T, C) float32 tensor, got "
+                             f"{(z.dtype, tuple(z.shape)) if isinstance(z, torch.Tensor) else type(z).__name__}")
+    if z1.shape != z2.shape:
+        raise ValueError(f"{who}: z1 {tuple(z1.shape)} and z2 {tuple(z2.shape)} differ in shape")
+    B, T, C = z1.shape
+    if C % 16 or not 16 <= C <= NCE_MAX_WIDTH:
+        raise ValueError(f"{who}: C = {C} is not a multiple of 16 in 16..{NCE_MAX_WIDTH}")
+    if B < 1 or T < 1:
+        raise ValueError(f"{who}: empty input {tuple(z1.shape)}")
+    groups, n = (B, T) if layout == "temporal" else (T, B)
+    if 2 * n > NCE_MAX_ROWS:
+        raise ValueError(f"{who}: a {layout} group has 2 * {n} rows, above {NCE_MAX_ROWS}")
+    if T * C >= 1 << 22:
+        raise ValueError(f"{who}: T * C = {T * C} must stay below 2^22")
+    if not z1.is_contiguous() or not z2.is_contiguous():
+        raise ValueError(f"{who}: z1 and z2 must be contiguous")
+    if z1.is_cuda and z1.device != z2.device:
+        raise ValueError(f"{who}: z1 and z2 are on different devices")
+    return (groups, n, C, T * C, C) if layout == "temporal" else (groups, n, C, C, T * C)
+
+
+def _nce_chunks(groups, layout):
+    """(first group, count) per launch: only the temporal layout (groups = B) can exceed the per-launch bound, and
+    its groups are contiguous slabs."""
+    return [(o, min(NCE_MAX_GROUPS, groups - o)) for o in range(0, groups, NCE_MAX_GROUPS)]
+
+
+def nce_rows_fwd(z1, z2, layout, lse=None, row_loss=None, stream=None):
+    """aw_nce_rows_fwd: the paired InfoNCE of contiguous (B, T, C) f32 device tensors, per row.  layout 'temporal':
+    groups = B sequences of 2 T rows; 'instance': groups = T steps of 2 B rows.  Returns (lse, row_loss), each
+    (groups, 2 n) f32: rows 0..n-1 of a group are z1's, n..2n-1 z2's."""
+    who = "nce_rows_fwd"
+    groups, n, c, gs, rs = _nce_geometry(z1, z2, layout, who)
+    p1, p2 = ptr(z1), ptr(z2)
+    dev = z1.device
+    if lse is None:
+        lse = torch.empty((groups, 2 * n), dtype=torch.float32, device=dev)
+    if row_loss is None:
+        row_loss = torch.empty((groups, 2 * n), dtype=torch.float32, device=dev)
+    _ts_act(lse, "lse", groups, 2 * n, who, dev)
+    _ts_act(row_loss, "row_loss", groups, 2 * n, who, dev)
+    for o, m in _nce_chunks(groups, layout):
+        _maybe_timed(stream, "nce_rows_fwd", 2.0 * m * (2 * n) ** 2 * c, lambda s: call(
+            "aw_nce_rows_fwd", p1 + 4 * o * gs, p2 + 4 * o * gs, m, n, c, gs, rs, ptr(lse[o:o + m]),
+            ptr(row_loss[o:o + m]), s),
+            info=lambda: (f"nce_fwd_kernel {layout} n={n} c={c}", 4.0 * m * 2 * n * (c + 2)))
+    return lse, row_loss
+
+
+def nce_rows_bwd(z1, z2, layout, lse, scale, dz1, dz2, accumulate=False, stream=None):
+    """aw_nce_rows_bwd: dz (+)= scale * d(sum of row_loss)/dz with the forward's lse; dz1 / dz2 are contiguous f32
+    tensors of z1's shape, overwritten, or added to with accumulate."""
+    who = "nce_rows_bwd"
+    groups, n, c, gs, rs = _nce_geometry(z1, z2, layout, who)
+    p1, p2 = ptr(z1), ptr(z2)
+    dev = z1.device
+    _ts_act(lse, "lse", groups, 2 * n, who, dev)
+    for nm, t in (("dz1", dz1), ("dz2", dz2)):
+        if (t is None or t.dtype != torch.float32 or t.shape != z1.shape or not t.is_contiguous()
+                or t.device != dev):
+            raise nat.NativeError(f"{who}: {nm} must be a contiguous float32 tensor of shape {tuple(z1.shape)} on the "
+                                  f"inputs' device")
+    d1, d2 = ptr(dz1), ptr(dz2)
+    for o, m in _nce_chunks(groups, layout):
+        _maybe_timed(stream, "nce_rows_bwd", 2.0 * m * (2 * n) ** 2 * c * (1 + -(-c // 128)), lambda s: call(
+            "aw_nce_rows_bwd", p1 + 4 * o * gs, p2 + 4 * o * gs, m, n, c, gs, rs, ptr(lse[o:o + m]), float(scale),
+            d1 + 4 * o * gs, d2 + 4 * o * gs, int(bool(accumulate)), s),
+            info=lambda: (f"nce_bwd_kernel {layout} n={n} c={c}", 4.0 * m * 2 * n * (2 * c + 1)))
+    return dz1, dz2
+
+
+def _pool2_check(x, who):
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"{who}: the input must be a contiguous (B, T, C) float32 tensor")
+    B, T, C = x.shape
+    if C % 16 or not 16 <= C <= NCE_MAX_WIDTH:
+        raise ValueError(f"{who}: C = {C} is not a multiple of 16 in 16..{NCE_MAX_WIDTH}")
+    if not 2 <= T <= nat.AW_TS_MAX_T:
+        raise ValueError(f"{who}: T = {T} outside 2..{nat.AW_TS_MAX_T}")
+    return B, T, C
+
+
+def ts_pool2_fwd(x, out=None, stream=None):
+    """aw_ts_pool2_fwd: max over pairs of time steps, (B, T, C) -> (B, T // 2, C) (an odd last step is dropped)."""
+    who = "ts_pool2_fwd"
+    B, T, C = _pool2_check(x, who)
+    px = ptr(x)
+    if out is None:
+        out = torch.empty((B, T // 2, C), dtype=torch.float32, device=x.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != (B, T // 2, C) or not out.is_contiguous() \
+            or out.device != x.device:
+        raise nat.NativeError(f"{who}: out must be a contiguous float32 tensor of shape {(B, T // 2, C)}")
+    for o in range(0, B, nat.AW_TS_MAX_BATCH):
+        m = min(nat.AW_TS_MAX_BATCH, B - o)
+        call("aw_ts_pool2_fwd", px + 4 * o * T * C, m, T, C, ptr(out[o:o + m]), stream_ptr(stream))
+    return out
+
+
+def ts_pool2_bwd(x, dout, din, stream=None):
+    """aw_ts_pool2_bwd: din[b, 2 t + k] += dout[b, t] at the step k the forward took from x (the first on a tie)."""
+    who = "ts_pool2_bwd"
+    B, T, C = _pool2_check(x, who)
+    px = ptr(x)
+    if dout.dtype != torch.float32 or tuple(dout.shape) != (B, T // 2, C) or not dout.is_contiguous() \
+            or dout.device != x.device:
+        raise nat.NativeError(f"{who}: dout must be a contiguous float32 tensor of shape {(B, T // 2, C)}")
+    if din.dtype != torch.float32 or din.shape != x.shape or not din.is_contiguous() or din.device != x.device:
+        raise nat.NativeError(f"{who}: din must be a contiguous float32 tensor of shape {tuple(x.shape)}")
+    pd = ptr(din)
+    for o in range(0, B, nat.AW_TS_MAX_BATCH):
+        m = min(nat.AW_TS_MAX_BATCH, B - o)
+        call("aw_ts_pool2_bwd", px + 4 * o * T * C, ptr(dout[o:o + m]), m, T, C, pd + 4 * o * T * C,
+             stream_ptr(stream))
+    return din
+
+
 # ------------------------------------------------------------------------------------------ layouts
 def patchify(x, P, out, stream=None):
     B, L, C = x.shape

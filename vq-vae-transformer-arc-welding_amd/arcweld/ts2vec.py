@@ -17,8 +17,15 @@ The forward, per sequence (B, T, C_in):
 Each convolution is one launch over the batch chunk (arcweld.kernels.ts_conv); GELU is applied once per element in the
 producing epilogue, the last convolution reduces over time itself for encoding_window='full_series'.
 
-Training (``fit``: the hierarchical contrastive loss, random crops and masks, AdamW, the SWA average) is not built: a
-checkpoint written by the reference is the input.  There is no CPU path.
+Training (model.ts2vec.TS2Vec.fit) stands on this module too:
+
+  hierarchical_contrastive_loss, instance_contrastive_loss, temporal_contrastive_loss
+                       the reference's losses.py as autograd functions over f32 device tensors, on the fused kernels
+                       of csrc/ts2vec_loss.hip: no (2T, 2T) similarity is ever written, the extra memory is O(B T C)
+  TSEncoder.train_forward   the differentiable forward on torch ops (F.linear / F.gelu / F.conv1d, autograd) with the
+                       random masks; the convolutions' backward on HIP is the follow-up
+  take_per_row, split_with_nan, centerize_vary_length_series, draw_crops, swa_update   what ``fit`` is made of
+There is no CPU path for ``encode`` or the loss.
 """
 from __future__ import annotations
 
@@ -26,12 +33,16 @@ from collections import OrderedDict
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 from torch import nn
 
 from . import _native as nat
 
 __all__ = ["TSEncoder", "strip_averaged", "averaged_state_dict", "encoder_from_state_dict", "load_checkpoint",
-           "MAX_T", "MAX_WIDTH", "MAX_INPUT_DIMS", "MAX_DEPTH", "WORKSPACE_BYTES"]
+           "MAX_T", "MAX_WIDTH", "MAX_INPUT_DIMS", "MAX_DEPTH", "WORKSPACE_BYTES",
+           "hierarchical_contrastive_loss", "instance_contrastive_loss", "temporal_contrastive_loss",
+           "take_per_row", "split_with_nan", "centerize_vary_length_series", "draw_crops", "swa_update",
+           "binomial_mask", "continuous_mask"]
 
 MAX_T, MAX_WIDTH, MAX_INPUT_DIMS = nat.AW_TS_MAX_T, nat.AW_TS_MAX_WIDTH, nat.AW_TS_MAX_CIN
 MAX_DEPTH = nat.AW_TS_MAX_DILATION.bit_length() - 1          # the last block's dilation is 2^depth
@@ -216,6 +227,52 @@ class TSEncoder(nn.Module):
         """(B, T, input_dims) -> (B, T, output_dims): ``encode`` with encoding_window None (the eval forward)."""
         return self.encode(x, mask=mask)
 
+    # -------------------------------------------------------------------------------------------- training forward
+    def train_forward(self, x, mask="binomial"):
+        """The differentiable forward of training, (B, T, input_dims) -> (B, T, output_dims), on torch ops over this
+        module's own parameters (any device; autograd gives the backward).  ``x`` is only read.  A step with a NaN in
+        any channel, and a step the mask hides, is zero before and after input_fc.  mask: 'binomial' (each step kept
+        with probability 1/2, drawn as np.random.binomial(1, 0.5, (B, T))), 'continuous' (5 hidden runs of T // 10
+        steps per sequence, starts from np.random.randint), 'all_true', 'all_false', 'mask_last', or a (B, T) bool
+        tensor (False = hide); None is 'binomial'.  GELU is the exact erf form; the output passes
+        F.dropout(p = self.repr_dropout.p)."""
+        w = self.input_fc.weight
+        x = torch.as_tensor(x)
+        if x.dim() != 3 or x.shape[2] != self.input_dims or not x.is_floating_point():
+            raise ValueError(f"x: expected a floating-point (B, T, {self.input_dims}) tensor, got {tuple(x.shape)}")
+        x = x.to(w.device, w.dtype)
+        B, T = x.shape[:2]
+        if mask is None:
+            mask = "binomial"
+        if isinstance(mask, str):
+            if mask == "binomial":
+                mk = binomial_mask(B, T)
+            elif mask == "continuous":
+                mk = continuous_mask(B, T)
+            elif mask in _MASKS:
+                mk = torch.ones((B, T), dtype=torch.bool)
+                if mask == "all_false":
+                    mk.zero_()
+                elif mask == "mask_last":
+                    mk[:, -1] = False
+            else:
+                raise ValueError(f"mask: expected one of {_RANDOM_MASKS + _MASKS} or a (B, T) bool tensor, got {mask!r}")
+        else:
+            mk = torch.as_tensor(mask)
+            if mk.dtype != torch.bool or tuple(mk.shape) != (B, T):
+                raise ValueError(f"mask: expected a bool tensor of shape {(B, T)}, got {mk.dtype} {tuple(mk.shape)}")
+        keep = (mk.to(w.device) & ~torch.isnan(x).any(-1)).unsqueeze(-1)
+        zero = torch.zeros((), dtype=w.dtype, device=w.device)
+        h = F.linear(torch.where(keep, x, zero), w, self.input_fc.bias)
+        h = torch.where(keep, h, zero).transpose(1, 2)                       # (B, hidden, T)
+        for blk in self.feature_extractor.net:
+            d = blk.conv1.conv.dilation[0]
+            res = h if blk.projector is None else F.conv1d(h, blk.projector.weight, blk.projector.bias)
+            u = F.conv1d(F.gelu(h), blk.conv1.conv.weight, blk.conv1.conv.bias, padding=d, dilation=d)
+            u = F.conv1d(F.gelu(u), blk.conv2.conv.weight, blk.conv2.conv.bias, padding=d, dilation=d)
+            h = u + res
+        return F.dropout(h, p=self.repr_dropout.p, training=True).transpose(1, 2)
+
     def _forward_chunk(self, x, mask, m, T, pack, ws, result, pooled):
         from . import kernels as k
         (fc_w, fc_b), blocks = pack
@@ -285,3 +342,192 @@ def encoder_from_state_dict(state_dict, device=None):
 def load_checkpoint(path, device=None):
     """encoder_from_state_dict of the file ``TS2Vec.save`` wrote."""
     return encoder_from_state_dict(torch.load(path, map_location="cpu", weights_only=True), device=device)
+
+
+# ------------------------------------------------------------------------------------------------ training: the loss
+class _PairedNCE(torch.autograd.Function):
+    """The hierarchy of paired InfoNCE terms (csrc/ts2vec_loss.hip).  ``plan``: 'hierarchy', or the single level-0
+    term 'instance' / 'temporal'.  The forward keeps the pooled levels and one lse per row and term; the backward
+    recomputes the similarities tile by tile, deepest level first, and every level's gradient is written in one fixed
+    launch order (instance, temporal, then the un-pooled deeper gradient): the same bits every run."""
+
+    @staticmethod
+    def forward(ctx, z1, z2, alpha, temporal_unit, plan):
+        from . import kernels as k
+        a, b = z1.detach().contiguous(), z2.detach().contiguous()
+        levels, terms, d = [(a, b)], [], 0
+        total = torch.zeros((), dtype=torch.float64, device=a.device)
+
+        def term(level, layout, weight):
+            u, v = levels[level]
+            if weight == 0 or (u.shape[0] if layout == "instance" else u.shape[1]) == 1:
+                return                                   # a pair alone in its group: the term is exactly 0
+            lse, row_loss = k.nce_rows_fwd(u, v, layout)
+            terms.append((level, layout, weight, lse))
+            total.add_(row_loss.double().sum(), alpha=weight / row_loss.numel())
+
+        if plan != "hierarchy":
+            term(0, plan, 1.0)
+            d = 1
+        else:
+            while levels[-1][0].shape[1] > 1:
+                term(len(levels) - 1, "instance", alpha)
+                if d >= temporal_unit:
+                    term(len(levels) - 1, "temporal", 1 - alpha)
+                d += 1
+                levels.append(tuple(k.ts_pool2_fwd(t) for t in levels[-1]))
+            term(len(levels) - 1, "instance", alpha)
+            d += 1
+        ctx.levels, ctx.terms, ctx.depth = levels, terms, d
+        return (total / d).float()
+
+    @staticmethod
+    def backward(ctx, gout):
+        from . import kernels as k
+        levels, g = ctx.levels, float(gout)
+        deeper = None
+        for level in range(len(levels) - 1, -1, -1):
+            u, v = levels[level]
+            du, dv = torch.empty_like(u), torch.empty_like(v)
+            written = False
+            for lv, layout, weight, lse in ctx.terms:
+                if lv == level:
+                    k.nce_rows_bwd(u, v, layout, lse, g * weight / (ctx.depth * lse.numel()), du, dv,
+                                   accumulate=written)
+                    written = True
+            if not written:
+                du.zero_(), dv.zero_()
+            if deeper is not None:
+                k.ts_pool2_bwd(u, deeper[0], du)
+                k.ts_pool2_bwd(v, deeper[1], dv)
+            deeper = (du, dv)
+        return deeper[0], deeper[1], None, None, None
+
+
+def _loss_args(z1, z2, temporal_unit, instance, temporal, who):
+    """Everything the kernels would refuse, as a ValueError before the device is looked at or anything is launched."""
+    from . import kernels as k
+    for nm, z in (("z1", z1), ("z2", z2)):
+        if not isinstance(z, torch.Tensor) or z.dim() != 3 or z.dtype != torch.float32:
+            raise ValueError(f"{who}: {nm} must be a (B, T, C) float32 tensor, got "
+                             f"{(z.dtype, tuple(z.shape)) if isinstance(z, torch.Tensor) else type(z).__name__}")
+    if z1.shape != z2.shape:
+        raise ValueError(f"{who}: z1 {tuple(z1.shape)} and z2 {tuple(z2.shape)} differ in shape")
+    B, T, C = z1.shape
+    if B < 1 or T < 1:
+        raise ValueError(f"{who}: empty input {tuple(z1.shape)}")
+    if C % 16 or not 16 <= C <= k.NCE_MAX_WIDTH:
+        raise ValueError(f"{who}: C = {C} is not a multiple of 16 in 16..{k.NCE_MAX_WIDTH}")
+    if T * C >= 1 << 22:
+        raise ValueError(f"{who}: T * C = {T * C} must stay below 2^22")
+    if instance and 2 * B > k.NCE_MAX_ROWS:
+        raise ValueError(f"{who}: the instance term has 2 B = {2 * B} rows per group, above {k.NCE_MAX_ROWS}")
+    if temporal and 2 * (T >> temporal_unit) > k.NCE_MAX_ROWS:
+        raise ValueError(f"{who}: the temporal term has 2 T = {2 * (T >> temporal_unit)} rows per group at its "
+                         f"first level, above {k.NCE_MAX_ROWS}")
+    if not z1.is_cuda or not z2.is_cuda:
+        raise nat.NativeError(f"{who} runs on the HIP kernels: pass device tensors (there is no CPU path)")
+    if z1.device != z2.device:
+        raise ValueError(f"{who}: z1 and z2 are on different devices")
+
+
+def hierarchical_contrastive_loss(z1, z2, alpha=0.5, temporal_unit=0):
+    """The reference's hierarchical contrastive loss of two views (B, T, C), f32 on the device, differentiable in both:
+    at every level of a max-pool pyramid over time (kernel 2, an odd last step dropped) alpha times the instance term
+    (across the batch, per step) plus, from level ``temporal_unit`` on, (1 - alpha) times the temporal term (across
+    time, per sequence); one more instance term at length 1; the sum divided by the number of levels.  A term whose
+    weight is 0 is skipped.  Non-contiguous views are copied.  The sum is accumulated in f64 in a fixed order."""
+    alpha, temporal_unit = float(alpha), int(temporal_unit)
+    if temporal_unit < 0:
+        raise ValueError(f"temporal_unit: expected an int >= 0, got {temporal_unit}")
+    _loss_args(z1, z2, temporal_unit, alpha != 0, 1 - alpha != 0, "hierarchical_contrastive_loss")
+    return _PairedNCE.apply(z1, z2, alpha, temporal_unit, "hierarchy")
+
+
+def instance_contrastive_loss(z1, z2):
+    """The instance term alone: per time step, each of the 2 B rows against the others, its pair the positive."""
+    _loss_args(z1, z2, 0, True, False, "instance_contrastive_loss")
+    return _PairedNCE.apply(z1, z2, 1.0, 0, "instance")
+
+
+def temporal_contrastive_loss(z1, z2):
+    """The temporal term alone: per sequence, each of the 2 T rows against the others, its pair the positive."""
+    _loss_args(z1, z2, 0, False, True, "temporal_contrastive_loss")
+    return _PairedNCE.apply(z1, z2, 1.0, 0, "temporal")
+
+
+# ------------------------------------------------------------------------------------------------ training: data
+def binomial_mask(B, T, p=0.5):
+    """(B, T) bool, True = keep, one np.random.binomial draw of the whole array."""
+    return torch.from_numpy(np.random.binomial(1, p, size=(B, T))).to(torch.bool)
+
+
+def continuous_mask(B, T, n=5, l=0.1):
+    """(B, T) bool with n runs of l hidden steps per sequence (a float counts in fractions of T); the starts come
+    from np.random.randint, sequence by sequence."""
+    n = int(n * T) if isinstance(n, float) else n
+    l = int(l * T) if isinstance(l, float) else l
+    n, l = max(min(n, T // 2), 1), max(l, 1)
+    keep = torch.ones((B, T), dtype=torch.bool)
+    for i in range(B):
+        for _ in range(n):
+            t0 = np.random.randint(T - l + 1)
+            keep[i, t0:t0 + l] = False
+    return keep
+
+
+def take_per_row(A, indx, num_elem):
+    """out[i] = A[i, indx[i] : indx[i] + num_elem]: a window per row, all of one length."""
+    cols = torch.as_tensor(np.asarray(indx)).reshape(-1, 1) + torch.arange(num_elem)
+    return A[torch.arange(cols.shape[0]).unsqueeze(1), cols]
+
+
+def split_with_nan(x, sections, axis=0):
+    """np.array_split into ``sections`` along ``axis``, the shorter pieces padded at the end with NaN to the length of
+    the first."""
+    if x.dtype not in (np.float16, np.float32, np.float64):
+        raise ValueError(f"split_with_nan: a floating-point array is needed to hold NaN, got {x.dtype}")
+    parts = np.array_split(x, sections, axis=axis)
+    full = parts[0].shape[axis]
+    out = []
+    for part in parts:
+        pad = [(0, 0)] * x.ndim
+        pad[axis] = (0, full - part.shape[axis])
+        out.append(np.pad(part, pad, mode="constant", constant_values=np.nan) if pad[axis][1] > 0 else part)
+    return out
+
+
+def centerize_vary_length_series(x):
+    """(n, T, C) series padded with all-NaN steps at either end, each rotated so that its valid span is centred."""
+    valid = ~np.isnan(x).all(axis=-1)
+    lead, trail = np.argmax(valid, axis=1), np.argmax(valid[:, ::-1], axis=1)
+    shift = (lead + trail) // 2 - lead
+    T = x.shape[1]
+    src = (np.arange(T)[None, :] - shift[:, None]) % T
+    return np.take_along_axis(x, src[:, :, None], axis=1)
+
+
+def draw_crops(ts_l, batch, temporal_unit=0):
+    """One iteration's crops from np.random in the reference's order -- crop_l, crop_left, crop_eleft, crop_eright,
+    then the per-row offsets -- so that a seeded run is replayable.  Returns a dict; view 1 is
+    take_per_row(x, offset + eleft, right - eleft)'s last crop_l steps, view 2 take_per_row(x, offset + left,
+    eright - left)'s first crop_l: the same crop_l steps of every row."""
+    crop_l = int(np.random.randint(low=2 ** (temporal_unit + 1), high=ts_l + 1))
+    left = int(np.random.randint(ts_l - crop_l + 1))
+    right = left + crop_l
+    eleft = int(np.random.randint(left + 1))
+    eright = int(np.random.randint(low=right, high=ts_l + 1))
+    offset = np.random.randint(low=-eleft, high=ts_l - eright + 1, size=batch)
+    return dict(crop_l=crop_l, left=left, right=right, eleft=eleft, eright=eright, offset=offset)
+
+
+@torch.no_grad()
+def swa_update(averaged, current, n_averaged):
+    """The running mean of torch's AveragedModel over parameters: avg += (p - avg) / (n_averaged + 1), a copy when
+    n_averaged is 0.  Returns n_averaged + 1."""
+    for avg, p in zip(averaged.parameters(), current.parameters()):
+        if n_averaged == 0:
+            avg.copy_(p)
+        else:
+            avg.add_((p.detach().to(avg.device) - avg) / (n_averaged + 1))
+    return n_averaged + 1

@@ -166,6 +166,36 @@ __device__ __forceinline__ void dots(const float* sb, int tid, f32x16 (&acc)[2][
   }
 }
 
+// The MFMAs of `dots` alone, on any two staged row sets: acc[mi][ni] += rows 64 (w >> 1) + 32 mi + .. of sa (row
+// stride LDA floats) against rows 64 (w & 1) + 32 ni + .. of sq (row stride LDQ) over K dims, in the order of `dots`
+// (step 4 g + t multiplies dims 8 g + t and 8 g + 4 + t).  mfma_dots<LD, LD, TD>(sb + TB * LD, sb, ..) is `dots`
+// without the norms (ts2vec_loss.hip, whose second GEMM also runs on it with the pair index as the dims).
+template <int LDA, int LDQ, int K>
+__device__ __forceinline__ void mfma_dots(const float* sa_rows, const float* sq_rows, int tid, f32x16 (&acc)[2][2]) {
+  static_assert(K % 8 == 0 && LDA % 4 == 0 && LDQ % 4 == 0, "16-byte LDS reads");
+  const int lane = tid & 63, w = tid >> 6, h = lane >> 5, jr = lane & 31;
+  const float* sa = sa_rows + (64 * (w >> 1) + jr) * LDA + 4 * h;
+  const float* sq = sq_rows + (64 * (w & 1) + jr) * LDQ + 4 * h;
+#pragma unroll
+  for (int g = 0; g < K / 8; ++g) {
+    float4 a4[2], b4[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      a4[t] = *reinterpret_cast<const float4*>(sa + 32 * t * LDA + 8 * g);
+      b4[t] = *reinterpret_cast<const float4*>(sq + 32 * t * LDQ + 8 * g);
+    }
+    const float av[2][4] = {{a4[0].x, a4[0].y, a4[0].z, a4[0].w}, {a4[1].x, a4[1].y, a4[1].z, a4[1].w}};
+    const float bv[2][4] = {{b4[0].x, b4[0].y, b4[0].z, b4[0].w}, {b4[1].x, b4[1].y, b4[1].z, b4[1].w}};
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4)
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mi][s4], bv[ni][s4], acc[mi][ni], 0, 0, 0);
+  }
+}
+
 // The finished tile to LDS: out[al * OT + bl] = f(fma(-2, dot, fl(|b|^2 + |a|^2))) for a row al against b row bl.
 // 2 dot is exact, so the fma's one rounding is that of fl(fl(|b|^2 + |a|^2) - 2 dot).  nrm_s has TB + TA floats; out
 // may overlay the stages: the first barrier publishes the norms and ends every wave's reading of the stages, the
